@@ -110,6 +110,46 @@ def lib_sha16():
     return None
 
 
+DUMP_MAX_ELEMS = 1 << 21     # per array: 8 MB of float32, four arenas + the loss stay far below 64 MB
+DUMP_SEED = 0
+
+
+def _dump_sample(a):
+  """The whole array when small, else a fixed seeded sample of DUMP_MAX_ELEMS positions (sorted, the same positions for
+  every arena of the same length, so weights / momentum / gradient line up element for element)."""
+  a = a.reshape(-1)
+  if a.size <= DUMP_MAX_ELEMS:
+    return a
+  import numpy as np
+  idx = np.sort(np.random.RandomState(DUMP_SEED).randint(0, a.size, DUMP_MAX_ELEMS))
+  return a[idx]
+
+
+def snapshot_outputs(g, inner, loss):
+  """What the last timed step handed its caller, copied to host float32 arrays: the loss it returned and the state it
+  left in the flat arenas (weights, dense gradient, Nesterov momentum, 0/1 mask over the masked segment)."""
+  import numpy as np
+  from rigl_amd import variables
+  out = {'loss': np.asarray([float(loss.detach().float().item())], dtype=np.float32)}
+  out['weights'] = _dump_sample(g.W.detach().cpu().numpy())
+  out['grad'] = _dump_sample(g.G.detach().cpu().numpy())
+  if getattr(inner, '_slot', None) is not None:
+    out['momentum'] = _dump_sample(inner._slot.detach().cpu().numpy())   # pylint: disable=protected-access
+  n_masked = g.seg[variables.KIND_MASKED][1]
+  if n_masked > 0:
+    words = g.BITS.detach().cpu().numpy().view(np.uint8)
+    bits = np.unpackbits(words, bitorder='little')[:n_masked]
+    out['mask'] = _dump_sample(bits.astype(np.float32))
+  return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+
+
+def write_outputs(directory, arrays):
+  import numpy as np
+  os.makedirs(directory, exist_ok=True)
+  for name, a in arrays.items():
+    np.save(os.path.join(directory, name + '.npy'), a)
+
+
 def _claim_stdout():
   """The contract is ONE JSON line on stdout.  RCCL prints a version banner through C stdio on rank 0 (buffered, so it
   lands AFTER anything Python printed when stdout is a pipe or a file), and libraries may print more: everything written
@@ -176,7 +216,14 @@ def main():
   ap.add_argument('--prof-every', type=int, default=10,
                   help='HIP-event timing of the K1 launches on every Nth timed step (1 = every step); the stamped '
                        'dispatches cost ~4 us each in the queue, 0.7 ms per fully profiled step')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the '
+                       'loss it returned and the weights, dense gradient, momentum and 0/1 mask it left behind -- whole '
+                       'when at most %d elements, else the same fixed seeded sample of that many positions (rank 0)'
+                       % DUMP_MAX_ELEMS)
   args = ap.parse_args()
+  if args.steps < 1:
+    ap.error('--steps must be at least 1')
 
   world = int(os.environ.get('WORLD_SIZE', '1'))
   rank = int(os.environ.get('RANK', '0'))
@@ -269,6 +316,7 @@ def main():
   n_updates = 0
   n_profiled = 0
   n_profiled_updates = 0
+  loss = None
   for i in range(args.steps):
     if in_loop_prof:
       upd = opt.is_mask_update_iter(int(gs.value), opt._last_update_step)   # (pure host arithmetic; the step recomputes it)
@@ -276,13 +324,15 @@ def main():
       ops.prof_enable(on)                  # a flag flip; the events are read after the timed region
       n_profiled += int(on)
     before = gs.value
-    run_step()
+    loss = run_step()
     is_upd = int(gs.value == before)
     n_updates += is_upd
     if in_loop_prof and on:
       n_profiled_updates += is_upd
   fence()
   dt = time.perf_counter() - t0
+  # (before anything below runs more steps: the graphed path's profiled eager steps, the exposed-communication probe)
+  dumped = snapshot_outputs(g, inner, loss) if (args.dump_outputs and rank == 0) else None
   prof = None
   if not args.no_prof and graphed is not None:
     # graph replays carry no per-kernel events: time the kernels on a few EAGER steps after the timed region
@@ -480,6 +530,8 @@ def main():
       except Exception as e:  # pylint: disable=broad-except
         out['cpu_baseline'] = {'value': None, 'unit': 'images/sec', 'cores': os.cpu_count(), 'kind': 'port',
                                'sample': 'failed: %r' % (e,)}
+    if dumped is not None:
+      write_outputs(args.dump_outputs, dumped)
     os.write(real_stdout, (json.dumps(out) + '\n').encode())
   if sync is not None:
     dist.barrier()
