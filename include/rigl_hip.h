@@ -157,6 +157,33 @@ int rigl_prune_regrow_selections(const RiglPruneRegrowLayer* layer /* host */,
                                  void* workspace, size_t workspace_bytes,
                                  rigl_stream_t stream);
 
+/* Two-slot forms for inner optimizers with a second slot per weight (Adam's m
+ * and v).  The reference resets EVERY slot of a grown connection
+ * (sparse_optimizers_base.py:345-353 SET, :555-564 RigL): momentum2[l] (a HOST
+ * array of n_layers device pointers, entries nullable; fp32 [n] each) receives
+ * the same reset value as layers[l].momentum -- 0 (RIGL_MOMRESET_ZEROS) or
+ * dense_grad * initial_acc_scale (RIGL_MOMRESET_GRAD; then dense_grad is
+ * required when initial_acc_scale != 0, as for momentum).  Everything else is
+ * rigl_prune_regrow / rigl_prune_regrow_selections; momentum2 == NULL is
+ * exactly those calls.  Workspaces as for the one-slot forms.
+ * Replaces: the per-slot tf.where / assign loop of reset_momentum for
+ *   tf.train.AdamOptimizer (imagenet_train_eval.py:355-358 --use_adam,
+ *   mnist_train_eval.py:247-261 --optimizer=adam).                         */
+int rigl_prune_regrow_slots(const RiglPruneRegrowLayer* layers /* host */,
+                            float* const* momentum2 /* host [n_layers], nullable */,
+                            int32_t n_layers, const RiglPruneRegrowParams* params,
+                            int32_t* out_counts /* device, 8*n_layers, nullable */,
+                            void* workspace /* device */, size_t workspace_bytes,
+                            rigl_stream_t stream);
+int rigl_prune_regrow_selections_slots(const RiglPruneRegrowLayer* layer /* host */,
+                                       float* momentum2 /* device fp32 [n], nullable */,
+                                       const RiglPruneRegrowParams* params,
+                                       uint32_t* out_mask1_bits, uint32_t* out_mask2_bits,
+                                       int32_t* out_idx1, int32_t* out_idx2,
+                                       int32_t* out_counts /* device, 8, nullable */,
+                                       void* workspace, size_t workspace_bytes,
+                                       rigl_stream_t stream);
+
 /* One-shot "keep the k best" mask (SNIP / DNW, sparse_optimizers.py:287-317,
  * :430-460): mask = the n_keep entries of score with the largest value, ties
  * by lower index.  Uses the same selection kernels as rigl_prune_regrow.    */
@@ -196,6 +223,38 @@ int rigl_masked_sgd_momentum(int64_t n, float* w, float* momentum,
                              float lr, float mu, float weight_decay,
                              float grad_scale, int32_t nesterov,
                              rigl_bf16* w_shadow, rigl_stream_t stream);
+
+/* K3-Adam: masked fused Adam update (+ bf16 shadow of mask*W).
+ * Replaces: the TF ApplyAdam kernel (training_ops.cc, use_nesterov=false)
+ *   behind tf.train.AdamOptimizer (imagenet_train_eval.py:214-215, 355-358
+ *   --use_adam; mnist_train_eval.py:247-261 --optimizer=adam), together with
+ *   the `mask *` of the masked-weight gradient and the l2 gradient:
+ *     alpha = (lr * sqrt(1 - beta_powers[1])) / (1 - beta_powers[0])
+ *     g     = (mask ? grad_scale*dense_grad : 0) + weight_decay * w
+ *     m     = m + (g - m) * (1 - beta1)
+ *     v     = v + (g*g - v) * (1 - beta2)
+ *     w     = w - (m * alpha) / (sqrt(v) + epsilon)
+ *   every product / sum rounded to fp32 separately, sqrt and division
+ *   correctly rounded: bit-identical to TF's fp32 CPU kernel.
+ * Masked-off weights are updated too (the reference applies Adam to the raw
+ * variable: a pruned weight gets g = weight_decay*w and keeps drifting on its
+ * old m); w_shadow (nullable) receives bf16(mask ? w_new : 0).
+ * beta_powers is a DEVICE fp32 [2] = {beta1^t, beta2^t} (the optimizer's
+ * non-slot variables); alpha is derived from it inside the kernel, so a
+ * captured HIP graph replays the current bias correction, not a frozen one.
+ * Alignment: w, m, v, dense_grad 16-byte, w_shadow 8-byte, mask_bits and
+ * beta_powers 4-byte (RIGL_EINVAL otherwise).  mask_bits == NULL = all ones. */
+int rigl_masked_adam(int64_t n, float* w, float* m, float* v,
+                     const float* dense_grad, const uint32_t* mask_bits,
+                     const float* beta_powers /* device [2] */, float lr,
+                     float beta1, float beta2, float epsilon,
+                     float weight_decay, float grad_scale,
+                     rigl_bf16* w_shadow, rigl_stream_t stream);
+/* beta_powers[0] *= beta1; beta_powers[1] *= beta2 (fp32, one rounding each):
+ * AdamOptimizer._finish, enqueued once after the last rigl_masked_adam of a
+ * step.  One single-lane launch.                                            */
+int rigl_adam_advance(float* beta_powers /* device [2] */, float beta1,
+                      float beta2, rigl_stream_t stream);
 
 /* bf16 shadows of mask*W for the conv kernels:  hwio[i] = bf16(mask_i?w_i:0)
  * in flat HWIO order (dgrad operand) and ohwi = the [cout][kh*kw*cin]
@@ -703,6 +762,11 @@ int rigl_eval_metrics(int32_t rows, int32_t classes, const rigl_bf16* logits,
 #define RIGL_PROF_KINDS 8
 int rigl_prof_enable(int32_t on);
 int rigl_prof_collect(double* ms_per_kind /*[8]*/, int64_t* launches /*[8]*/);
+/* The same over the first n_kinds (<= RIGL_PROF_KINDS_ALL) families: kind
+ * 8 = masked_adam (rigl_masked_adam and rigl_adam_advance).  rigl_prof_collect
+ * keeps its eight-entry contract and drops kind 8's events.                 */
+#define RIGL_PROF_KINDS_ALL 9
+int rigl_prof_collect_kinds(double* ms_per_kind, int64_t* launches, int32_t n_kinds);
 /* The same events one by one, in launch order (instead of rigl_prof_collect,
  * which consumes them too): kind as above; tag = (h, w, cin, cout, kh, stride_h)
  * of the conv descriptor the launch belongs to (zeros for K2 / K3 / pack); ms =

@@ -17,7 +17,7 @@ RIGL_EWORKSPACE = -3
 RIGL_EUNSUPPORTED = -4
 COUNTS_PER_LAYER = 8
 PROF_KINDS = ('conv_fwd', 'conv_dgrad', 'conv_wgrad', 'prune_regrow',
-              'sgd_momentum', 'pack_weights', 'conv_bwd', 'depthwise')
+              'sgd_momentum', 'pack_weights', 'conv_bwd', 'depthwise', 'masked_adam')
 
 GROW_ZEROS, GROW_GRAD_SCALE, GROW_GRAD_SIGN, GROW_EXPLICIT = 0, 1, 2, 3
 MOMRESET_ZEROS, MOMRESET_GRAD = 0, 1
@@ -96,13 +96,19 @@ SIGNATURES = {
     'rigl_prune_regrow': (C.c_int, [C.POINTER(PruneRegrowLayer), _I32,
                                     C.POINTER(PruneRegrowParams), _P, _P, _SZ,
                                     _P]),
+    'rigl_prune_regrow_slots': (C.c_int, [C.POINTER(PruneRegrowLayer), C.POINTER(_P), _I32,
+                                          C.POINTER(PruneRegrowParams), _P, _P, _SZ, _P]),
     'rigl_prune_regrow_selections_workspace_bytes': (_SZ, [_I64]),
     'rigl_prune_regrow_selections': (C.c_int, [C.POINTER(PruneRegrowLayer), C.POINTER(PruneRegrowParams), _P, _P, _P, _P, _P,
                                                _P, _SZ, _P]),
+    'rigl_prune_regrow_selections_slots': (C.c_int, [C.POINTER(PruneRegrowLayer), _P, C.POINTER(PruneRegrowParams), _P, _P,
+                                                     _P, _P, _P, _P, _SZ, _P]),
     'rigl_topk_mask': (C.c_int, [_P, _I64, _I64, _P, _P, _SZ, _P]),
     'rigl_topk_mask_batched': (C.c_int, [C.POINTER(TopkLayer), _I32, _P, _SZ, _P]),
     'rigl_masked_sgd_momentum': (C.c_int, [_I64, _P, _P, _P, _P, _F, _F, _F, _F,
                                            _I32, _P, _P]),
+    'rigl_masked_adam': (C.c_int, [_I64, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P, _P]),
+    'rigl_adam_advance': (C.c_int, [_P, _F, _F, _P]),
     'rigl_pack_weights': (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
     'rigl_pack_weights_batched': (C.c_int, [C.POINTER(PackLayer), _I32, _P]),
     'rigl_conv2d_workspace_bytes': (_SZ, [C.POINTER(ConvDesc), _I32]),
@@ -169,6 +175,7 @@ SIGNATURES = {
     'rigl_eval_metrics': (C.c_int, [_I32, _I32, _P, _P, _F, _I32, _P, _P, _P, _P]),
     'rigl_prof_enable': (C.c_int, [_I32]),
     'rigl_prof_collect': (C.c_int, [C.POINTER(C.c_double), C.POINTER(_I64)]),
+    'rigl_prof_collect_kinds': (C.c_int, [C.POINTER(C.c_double), C.POINTER(_I64), _I32]),
     'rigl_prof_collect_launches': (C.c_int, [C.POINTER(ProfLaunch), _I64, C.POINTER(_I64)]),
     'rigl_probe_mfma_bf16': (C.c_int, [_I32, _I32, _P, _P]),
     'rigl_tune_set': (C.c_int, [C.c_char_p, _I32]),

@@ -1,4 +1,4 @@
-// K3 (masked fused SGD / Nesterov momentum), mask bitmap pack/unpack and the
+// K3 (masked fused SGD / Nesterov momentum, masked Adam), mask bitmap pack/unpack and the
 // bf16 weight-shadow pack kernels.  All HBM-bound streaming kernels: 16 B per
 // lane coalesced accesses, grid-stride, no LDS except for the OHWI transpose.
 #include "common.hpp"
@@ -107,6 +107,86 @@ __global__ __launch_bounds__(BLOCK) void k_sgd(SgdArgs A) {
     A.w[e] = w;
     if (HAS_MOM) A.mom[e] = a;
     if (HAS_SHADOW) A.shadow[e] = on ? f2bf(w) : (uint16_t)0;
+  }
+}
+
+// ---- masked Adam (TF ApplyAdam, non-Nesterov) ---------------------------------------
+struct AdamArgs {
+  int64_t n;
+  float* w;
+  float* m;
+  float* v;
+  const float* g;
+  const uint32_t* mask;
+  const float* beta_powers;  // device {beta1^t, beta2^t}: read here, never a kernel argument (graph replay)
+  float lr, omb1, omb2, eps, wd, gscale;  // omb = (1 - beta), one fp32 subtraction each on the host
+  uint16_t* shadow;
+};
+
+// Correctly rounded fp32 sqrt.  (HIP's __fsqrt_rn is the approximate native sqrt unless OCML_BASIC_ROUNDED_OPERATIONS is
+// defined; llvm.sqrt.f32 without fpmath metadata is expanded to the IEEE-rounded result.  Division: plain `/` is correctly
+// rounded under HIP's default -fhip-fp32-correctly-rounded-divide-sqrt, which is what __fdiv_rn expands to.)
+__device__ __forceinline__ float sqrt_rn(float x) { return __builtin_sqrtf(x); }
+
+// Masked-off elements are updated as well (g = wd * w): the reference applies Adam to the raw variable.
+__device__ __forceinline__ void adam_one(float& w, float& m, float& v, float g, bool on, float alpha, const AdamArgs& A) {
+  float gm = on ? (A.gscale == 1.f ? g : __fmul_rn(g, A.gscale)) : 0.f;
+  float gv = A.wd != 0.f ? __fadd_rn(gm, __fmul_rn(A.wd, w)) : gm;        // the same g as sgd_one
+  m = __fadd_rn(m, __fmul_rn(__fsub_rn(gv, m), A.omb1));                     // m += (g - m) * (1 - beta1)
+  v = __fadd_rn(v, __fmul_rn(__fsub_rn(__fmul_rn(gv, gv), v), A.omb2));      // v += (g*g - v) * (1 - beta2)
+  w = __fsub_rn(w, __fdiv_rn(__fmul_rn(m, alpha), __fadd_rn(sqrt_rn(v), A.eps)));
+}
+
+template <bool HAS_MASK, bool HAS_SHADOW>
+__global__ __launch_bounds__(BLOCK) void k_adam(AdamArgs A) {
+  // alpha = (lr * sqrt(1 - beta2^t)) / (1 - beta1^t), in the order of ApplyAdam's functor, once per lane (uniform loads)
+  const float bp1 = A.beta_powers[0], bp2 = A.beta_powers[1];
+  const float alpha = __fdiv_rn(__fmul_rn(A.lr, sqrt_rn(__fsub_rn(1.f, bp2))), __fsub_rn(1.f, bp1));
+  const int64_t nq = A.n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * BLOCK;
+  for (int64_t qi = (int64_t)blockIdx.x * BLOCK + threadIdx.x; qi < nq; qi += stride) {
+    const int64_t e = qi << 2;
+    float4 w = *reinterpret_cast<const float4*>(A.w + e);
+    float4 g = *reinterpret_cast<const float4*>(A.g + e);
+    float4 m = *reinterpret_cast<const float4*>(A.m + e);
+    float4 v = *reinterpret_cast<const float4*>(A.v + e);
+    uint32_t nib = 0xFu;
+    if (HAS_MASK) nib = (A.mask[e >> 5] >> (uint32_t)(e & 31)) & 0xFu;
+    adam_one(w.x, m.x, v.x, g.x, nib & 1u, alpha, A);
+    adam_one(w.y, m.y, v.y, g.y, nib & 2u, alpha, A);
+    adam_one(w.z, m.z, v.z, g.z, nib & 4u, alpha, A);
+    adam_one(w.w, m.w, v.w, g.w, nib & 8u, alpha, A);
+    *reinterpret_cast<float4*>(A.w + e) = w;
+    *reinterpret_cast<float4*>(A.m + e) = m;
+    *reinterpret_cast<float4*>(A.v + e) = v;
+    if (HAS_SHADOW) {
+      ushort4 s;
+      s.x = (nib & 1u) ? f2bf(w.x) : (uint16_t)0;
+      s.y = (nib & 2u) ? f2bf(w.y) : (uint16_t)0;
+      s.z = (nib & 4u) ? f2bf(w.z) : (uint16_t)0;
+      s.w = (nib & 8u) ? f2bf(w.w) : (uint16_t)0;
+      *reinterpret_cast<ushort4*>(A.shadow + e) = s;
+    }
+  }
+  // tail (n % 4 elements), one thread each
+  const int64_t tail0 = nq << 2;
+  if (blockIdx.x == 0 && (int64_t)threadIdx.x < A.n - tail0) {
+    const int64_t e = tail0 + threadIdx.x;
+    float w = A.w[e], m = A.m[e], v = A.v[e];
+    bool on = HAS_MASK ? ((A.mask[e >> 5] >> (uint32_t)(e & 31)) & 1u) : true;
+    adam_one(w, m, v, A.g[e], on, alpha, A);
+    A.w[e] = w;
+    A.m[e] = m;
+    A.v[e] = v;
+    if (HAS_SHADOW) A.shadow[e] = on ? f2bf(w) : (uint16_t)0;
+  }
+}
+
+// AdamOptimizer._finish: the beta powers advance once per apply, fp32 products (not powf(beta, t))
+__global__ void k_adam_advance(float* __restrict__ bp, float beta1, float beta2) {
+  if (threadIdx.x == 0) {
+    bp[0] = __fmul_rn(bp[0], beta1);
+    bp[1] = __fmul_rn(bp[1], beta2);
   }
 }
 
@@ -263,6 +343,49 @@ int rigl_masked_sgd_momentum(int64_t n, float* w, float* momentum, const float* 
     default: hipLaunchKernelGGL((k3::k_sgd<true, true, true>), g, b, 0, s, A); break;
   }
   RIGL_CHECK_LAUNCH("rigl_masked_sgd_momentum");
+  return RIGL_OK;
+}
+
+int rigl_masked_adam(int64_t n, float* w, float* m, float* v, const float* dense_grad, const uint32_t* mask_bits,
+                     const float* beta_powers, float lr, float beta1, float beta2, float epsilon, float weight_decay,
+                     float grad_scale, rigl_bf16* w_shadow, rigl_stream_t stream) {
+  using namespace rigl;
+  if (n < 0 || (n > 0 && (!w || !m || !v || !dense_grad || !beta_powers)))
+    return fail(RIGL_EINVAL, "rigl_masked_adam: bad arguments");
+  if (n == 0) return RIGL_OK;
+  auto mis = [](const void* p, size_t a) { return p && (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+  if (mis(w, 16) || mis(m, 16) || mis(v, 16) || mis(dense_grad, 16) || mis(w_shadow, 8) || mis(mask_bits, 4) ||
+      mis(beta_powers, 4))
+    return fail(RIGL_EINVAL, "rigl_masked_adam: w/m/v/grad must be 16-byte aligned, shadow 8-byte");
+  k3::AdamArgs A;
+  A.n = n; A.w = w; A.m = m; A.v = v; A.g = dense_grad; A.mask = mask_bits; A.beta_powers = beta_powers;
+  A.lr = lr; A.omb1 = 1.f - beta1; A.omb2 = 1.f - beta2; A.eps = epsilon; A.wd = weight_decay; A.gscale = grad_scale;
+  A.shadow = w_shadow;
+  int64_t blocks = ceil_div64(ceil_div64(n, 4), k3::BLOCK);
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipStream_t s = as_stream(stream);
+  ProfScope prof(PROF_ADAM, s);
+  dim3 g((unsigned)blocks), b(k3::BLOCK);
+  const int sel = (mask_bits ? 2 : 0) | (w_shadow ? 1 : 0);
+  switch (sel) {
+    case 0: hipLaunchKernelGGL((k3::k_adam<false, false>), g, b, 0, s, A); break;
+    case 1: hipLaunchKernelGGL((k3::k_adam<false, true>), g, b, 0, s, A); break;
+    case 2: hipLaunchKernelGGL((k3::k_adam<true, false>), g, b, 0, s, A); break;
+    default: hipLaunchKernelGGL((k3::k_adam<true, true>), g, b, 0, s, A); break;
+  }
+  RIGL_CHECK_LAUNCH("rigl_masked_adam");
+  return RIGL_OK;
+}
+
+int rigl_adam_advance(float* beta_powers, float beta1, float beta2, rigl_stream_t stream) {
+  using namespace rigl;
+  if (!beta_powers || (reinterpret_cast<uintptr_t>(beta_powers) & 3u) != 0)
+    return fail(RIGL_EINVAL, "rigl_adam_advance: bad beta_powers");
+  hipStream_t s = as_stream(stream);
+  ProfScope prof(PROF_ADAM, s);
+  hipLaunchKernelGGL(k3::k_adam_advance, dim3(1), dim3(64), 0, s, beta_powers, beta1, beta2);
+  RIGL_CHECK_LAUNCH("rigl_adam_advance");
   return RIGL_OK;
 }
 

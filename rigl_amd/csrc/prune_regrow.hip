@@ -37,6 +37,7 @@ struct LayerDev {
   int64_t n;
   float* w;
   float* mom;
+  float* mom2;           // second optimizer slot (Adam's v), reset like mom; NULL = none
   uint32_t* mask;
   const float* g;
   const float* noise;
@@ -678,7 +679,7 @@ __global__ __launch_bounds__(BLOCK) void k_apply2(const LayerDev* __restrict__ L
       if (newc) {
         float gv[4] = {0.f, 0.f, 0.f, 0.f};
         const bool need_g = (prm.grow_init_mode == RIGL_GROW_GRAD_SCALE || prm.grow_init_mode == RIGL_GROW_GRAD_SIGN ||
-                             (L.mom && prm.momentum_reset_mode == RIGL_MOMRESET_GRAD));
+                             ((L.mom || L.mom2) && prm.momentum_reset_mode == RIGL_MOMRESET_GRAD));
         if (need_g && L.g) load4(L.g, q[j], gv);
         float ev[4] = {0.f, 0.f, 0.f, 0.f};
         if (prm.grow_init_mode == RIGL_GROW_EXPLICIT && L.gvals) load4(L.gvals, q[j], ev);
@@ -692,9 +693,9 @@ __global__ __launch_bounds__(BLOCK) void k_apply2(const LayerDev* __restrict__ L
               nw = __fdiv_rn(sg, prm.grow_init_div);
             } else if (prm.grow_init_mode == RIGL_GROW_EXPLICIT) nw = ev[v];
             L.w[q[j].e0 + v] = nw;
-            if (L.mom)
-              L.mom[q[j].e0 + v] =
-                  prm.momentum_reset_mode == RIGL_MOMRESET_GRAD ? __fmul_rn(gv[v], prm.initial_acc_scale) : 0.f;
+            const float reset = prm.momentum_reset_mode == RIGL_MOMRESET_GRAD ? __fmul_rn(gv[v], prm.initial_acc_scale) : 0.f;
+            if (L.mom) L.mom[q[j].e0 + v] = reset;
+            if (L.mom2) L.mom2[q[j].e0 + v] = reset;   // every slot of a grown connection (base.py:345-353, :555-564)
           }
         }
       }
@@ -846,7 +847,7 @@ static Layout make_layout(const int64_t* n_per_layer, int n_layers) {
 
 static int run(const RiglPruneRegrowLayer* layers, int n_layers, const int64_t* fixed_k, const Params& prm,
                bool with_grow, uint32_t* const* mask1_override, int32_t* out_counts, void* ws, size_t ws_bytes,
-               hipStream_t stream, const ExportDev* ex = nullptr) {
+               hipStream_t stream, const ExportDev* ex = nullptr, float* const* mom2 = nullptr) {
   if (n_layers <= 0) return RIGL_OK;
   std::vector<int64_t> ns(n_layers);
   for (int i = 0; i < n_layers; ++i) {
@@ -859,7 +860,8 @@ static int run(const RiglPruneRegrowLayer* layers, int n_layers, const int64_t* 
         if (!l.w) return fail(RIGL_EINVAL, "prune_regrow: layer %d: w is NULL", i);
         if (!l.score_grow && !l.dense_grad) return fail(RIGL_EINVAL, "prune_regrow: layer %d: no grow score (dense_grad and score_grow NULL)", i);
         if (!l.dense_grad && (prm.grow_init_mode == RIGL_GROW_GRAD_SCALE || prm.grow_init_mode == RIGL_GROW_GRAD_SIGN ||
-                              (l.momentum && prm.momentum_reset_mode == RIGL_MOMRESET_GRAD && prm.initial_acc_scale != 0.f)))
+                              ((l.momentum || (mom2 && mom2[i])) && prm.momentum_reset_mode == RIGL_MOMRESET_GRAD &&
+                               prm.initial_acc_scale != 0.f)))
           return fail(RIGL_EINVAL, "prune_regrow: layer %d: mode needs dense_grad", i);
         if (prm.grow_init_mode == RIGL_GROW_EXPLICIT && !l.grow_values) return fail(RIGL_EINVAL, "prune_regrow: layer %d: grow_values is NULL", i);
       }
@@ -881,7 +883,7 @@ static int run(const RiglPruneRegrowLayer* layers, int n_layers, const int64_t* 
   for (int i = 0; i < n_layers; ++i) {
     const RiglPruneRegrowLayer& l = layers[i];
     LayerDev& d = hL[i];
-    d.n = l.n; d.w = l.w; d.mom = l.momentum; d.mask = l.mask_bits; d.g = l.dense_grad; d.noise = l.drop_noise;
+    d.n = l.n; d.w = l.w; d.mom = l.momentum; d.mom2 = mom2 ? mom2[i] : nullptr; d.mask = l.mask_bits; d.g = l.dense_grad; d.noise = l.drop_noise;
     d.sdrop = l.score_drop; d.sgrow = l.score_grow; d.gvals = l.grow_values;
     d.mask1 = (mask1_override && mask1_override[i]) ? mask1_override[i] : mask1 + mw;
     d.chunk_begin = chunk;
@@ -953,6 +955,12 @@ size_t rigl_prune_regrow_workspace_bytes(const int64_t* n_per_layer, int32_t n_l
 
 int rigl_prune_regrow(const RiglPruneRegrowLayer* layers, int32_t n_layers, const RiglPruneRegrowParams* params,
                       int32_t* out_counts, void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
+  return rigl_prune_regrow_slots(layers, nullptr, n_layers, params, out_counts, workspace, workspace_bytes, stream);
+}
+
+int rigl_prune_regrow_slots(const RiglPruneRegrowLayer* layers, float* const* momentum2, int32_t n_layers,
+                            const RiglPruneRegrowParams* params, int32_t* out_counts, void* workspace, size_t workspace_bytes,
+                            rigl_stream_t stream) {
   if (!layers || !params) return rigl::fail(RIGL_EINVAL, "rigl_prune_regrow: NULL layers/params");
   if (n_layers < 0) return rigl::fail(RIGL_EINVAL, "rigl_prune_regrow: n_layers < 0");
   if (!(params->drop_fraction >= 0.f) || params->drop_fraction > 1.f)
@@ -967,7 +975,7 @@ int rigl_prune_regrow(const RiglPruneRegrowLayer* layers, int32_t n_layers, cons
   p.initial_acc_scale = params->initial_acc_scale;
   p.reinit_when_same = params->reinit_when_same;
   return rigl::k2::run(layers, n_layers, nullptr, p, true, nullptr, out_counts, workspace, workspace_bytes,
-                       rigl::as_stream(stream));
+                       rigl::as_stream(stream), nullptr, momentum2);
 }
 
 // ---- the two selections, read back -------------------------------------------------------------------------------------
@@ -1077,6 +1085,13 @@ size_t rigl_prune_regrow_selections_workspace_bytes(int64_t n) { return n > 0 ? 
 int rigl_prune_regrow_selections(const RiglPruneRegrowLayer* layer, const RiglPruneRegrowParams* params,
                                  uint32_t* out_mask1_bits, uint32_t* out_mask2_bits, int32_t* out_idx1, int32_t* out_idx2,
                                  int32_t* out_counts, void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
+  return rigl_prune_regrow_selections_slots(layer, nullptr, params, out_mask1_bits, out_mask2_bits, out_idx1, out_idx2,
+                                            out_counts, workspace, workspace_bytes, stream);
+}
+
+int rigl_prune_regrow_selections_slots(const RiglPruneRegrowLayer* layer, float* momentum2, const RiglPruneRegrowParams* params,
+                                       uint32_t* out_mask1_bits, uint32_t* out_mask2_bits, int32_t* out_idx1, int32_t* out_idx2,
+                                       int32_t* out_counts, void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
   if (!layer || !params) return rigl::fail(RIGL_EINVAL, "rigl_prune_regrow_selections: NULL layer/params");
   if (layer->n <= 0 || layer->n >= (int64_t(1) << 31)) return rigl::fail(RIGL_EINVAL, "rigl_prune_regrow_selections: n out of range");
   if ((out_idx1 == nullptr) != (out_idx2 == nullptr)) return rigl::fail(RIGL_EINVAL, "rigl_prune_regrow_selections: give both index lists or neither");
@@ -1096,7 +1111,8 @@ int rigl_prune_regrow_selections(const RiglPruneRegrowLayer* layer, const RiglPr
   p.drop_fraction = params->drop_fraction; p.grow_init_mode = params->grow_init_mode; p.grow_init_div = params->grow_init_div;
   p.momentum_reset_mode = params->momentum_reset_mode; p.initial_acc_scale = params->initial_acc_scale;
   p.reinit_when_same = params->reinit_when_same;
-  int rc = rigl::k2::run(layer, 1, nullptr, p, true, nullptr, out_counts, base + lo.k2ws, lo.total - lo.k2ws, st, &ex);
+  float* const mom2[1] = {momentum2};
+  int rc = rigl::k2::run(layer, 1, nullptr, p, true, nullptr, out_counts, base + lo.k2ws, lo.total - lo.k2ws, st, &ex, mom2);
   if (rc || !out_idx1) return rc;
   // stable descending sort of (selected, key): selected entries first, larger score first, equal scores by lower index
   unsigned long long* ko = reinterpret_cast<unsigned long long*>(base + lo.keys_out);

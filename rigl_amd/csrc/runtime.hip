@@ -79,7 +79,7 @@ static std::mutex g_prof_mu;
 static bool g_prof_on = false;
 static std::vector<EvPair> g_pending;
 static std::vector<hipEvent_t> g_pool;
-static thread_local hipEvent_t t_open[RIGL_PROF_KINDS];
+static thread_local hipEvent_t t_open[RIGL_PROF_KINDS_ALL];
 
 bool prof_enabled() { return g_prof_on; }
 
@@ -203,7 +203,13 @@ int rigl_prof_enable(int32_t on) {
 
 int rigl_prof_collect(double* ms_per_kind, int64_t* launches) {
   if (!ms_per_kind || !launches) return rigl::fail(RIGL_EINVAL, "rigl_prof_collect: NULL output");
-  for (int i = 0; i < RIGL_PROF_KINDS; ++i) { ms_per_kind[i] = 0.0; launches[i] = 0; }
+  return rigl_prof_collect_kinds(ms_per_kind, launches, RIGL_PROF_KINDS);
+}
+
+int rigl_prof_collect_kinds(double* ms_per_kind, int64_t* launches, int32_t n_kinds) {
+  if (!ms_per_kind || !launches || n_kinds < 0 || n_kinds > RIGL_PROF_KINDS_ALL)
+    return rigl::fail(RIGL_EINVAL, "rigl_prof_collect_kinds: NULL output or n_kinds out of range");
+  for (int i = 0; i < n_kinds; ++i) { ms_per_kind[i] = 0.0; launches[i] = 0; }
   std::vector<rigl::EvPair> pend;
   {
     std::lock_guard<std::mutex> l(rigl::g_prof_mu);
@@ -211,7 +217,7 @@ int rigl_prof_collect(double* ms_per_kind, int64_t* launches) {
   }
   for (auto& p : pend) {
     float ms = 0.f;
-    if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+    if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess && p.kind < n_kinds) {
       ms_per_kind[p.kind] += ms;
       launches[p.kind] += 1;
     }

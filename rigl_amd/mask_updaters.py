@@ -123,24 +123,32 @@ class MaskUpdater:
     return req
 
   def _run(self, reqs, drop_fraction, reinit_when_same):
-    # K2 resets ONE slot tensor per layer inside the launch; further slots (none of the
-    # optimizers here has more than one) are reset from the new-connection set below.
+    # K2 resets up to TWO slot tensors per layer inside the launch (momentum, or Adam's m and v); further slots
+    # are reset from the new-connection set of each layer, read back from the update itself: mask2 with
+    # reinit_when_same, else mask2 & ~old mask (the kernel's own rule, rigl_hip.h).
     names = list(self._optimizer.get_slot_names())
-    extra = []
+    layers = []
     for r in reqs:
       lv = r.pop('_lv')
       if names:
         r['momentum'] = self._optimizer.get_slot(lv.weights, names[0]).view(-1)
       if len(names) > 1:
-        extra.append((lv, ops.mask_unpack(lv.mask.bits, (lv.weights.numel,))))
-    ops.prune_regrow(reqs, float(drop_fraction), grow_init_mode=_lib.GROW_ZEROS,
-                     momentum_reset_mode=_lib.MOMRESET_ZEROS, initial_acc_scale=0.0,
-                     reinit_when_same=reinit_when_same)
-    for lv, old in extra:
-      new = ops.mask_unpack(lv.mask.bits, (lv.weights.numel,))
-      grown = (new > old) if not reinit_when_same else (new > 0)
-      for s_name in names[1:]:
-        self._optimizer.get_slot(lv.weights, s_name).view(-1)[grown] = 0
+        r['momentum2'] = self._optimizer.get_slot(lv.weights, names[1]).view(-1)
+      layers.append(lv)
+    kw = dict(grow_init_mode=_lib.GROW_ZEROS, momentum_reset_mode=_lib.MOMRESET_ZEROS, initial_acc_scale=0.0,
+              reinit_when_same=reinit_when_same)
+    if len(names) <= 2:
+      ops.prune_regrow(reqs, float(drop_fraction), **kw)
+    else:
+      for r, lv in zip(reqs, layers):       # one layer per call: its mask2 comes back with it
+        n = lv.weights.numel
+        old = ops.mask_unpack(lv.mask.bits, (n,)) > 0
+        sel = ops.prune_regrow_selections(r, float(drop_fraction), want_indices=False, **kw)
+        grown = ops.mask_unpack(sel['mask2_bits'], (n,)) > 0
+        if not reinit_when_same:
+          grown &= ~old
+        for s_name in names[2:]:
+          self._optimizer.get_slot(lv.weights, s_name).view(-1)[grown] = 0
     self._graph.shadows_dirty = True
 
   def reset_momentum(self, var, new_connections):

@@ -104,8 +104,11 @@ def prune_regrow(layers, drop_fraction, grow_init_mode=_lib.GROW_ZEROS,
   """Runs the fused prune/regrow update on a list of layers, in place.
 
   Each layer is a dict with tensors: ``w`` (fp32), ``mask_bits`` (int32),
-  optional ``momentum``, ``dense_grad``, ``drop_noise``, ``score_drop``,
-  ``score_grow``, ``grow_values`` (all fp32, same numel as ``w``).
+  optional ``momentum``, ``momentum2``, ``dense_grad``, ``drop_noise``,
+  ``score_drop``, ``score_grow``, ``grow_values`` (all fp32, same numel as
+  ``w``).  ``momentum2`` is a second optimizer slot (Adam's v), reset like
+  ``momentum``; only when some layer has one does the call go to
+  rigl_prune_regrow_slots, otherwise it is rigl_prune_regrow.
   Returns an int32 tensor [n_layers, 8] of counts (see rigl_hip.h).
   """
   lib = _lib.load()
@@ -114,13 +117,14 @@ def prune_regrow(layers, drop_fraction, grow_init_mode=_lib.GROW_ZEROS,
     return torch.zeros((0, _lib.COUNTS_PER_LAYER), dtype=torch.int32)
   arr = (PruneRegrowLayer * nl)()
   ns = (C.c_int64 * nl)()
+  mom2 = (C.c_void_p * nl)()
   dev = None
   for i, l in enumerate(layers):
     w = l.get('w')
     ref = w if w is not None else l['score_drop']
     n = ref.numel()
     dev = ref.device
-    for key in ('w', 'momentum', 'dense_grad', 'drop_noise', 'score_drop',
+    for key in ('w', 'momentum', 'momentum2', 'dense_grad', 'drop_noise', 'score_drop',
                 'score_grow', 'grow_values'):
       t = l.get(key)
       _req(t, torch.float32, key, allow_none=True)
@@ -137,6 +141,8 @@ def prune_regrow(layers, drop_fraction, grow_init_mode=_lib.GROW_ZEROS,
       t = l.get(key)
       setattr(arr[i], key, t.data_ptr() if t is not None else None)
     arr[i].mask_bits = l['mask_bits'].data_ptr()
+    m2 = l.get('momentum2')
+    mom2[i] = m2.data_ptr() if m2 is not None else None
     ns[i] = n
   prm = PruneRegrowParams(float(drop_fraction), int(grow_init_mode),
                           float(grow_init_div), int(momentum_reset_mode),
@@ -145,8 +151,12 @@ def prune_regrow(layers, drop_fraction, grow_init_mode=_lib.GROW_ZEROS,
   ws = workspace(need, dev)
   counts = torch.zeros((nl, _lib.COUNTS_PER_LAYER), dtype=torch.int32,
                        device=dev)
-  check(lib.rigl_prune_regrow(arr, nl, C.byref(prm), _ptr(counts), _ptr(ws),
-                              ws.numel(), _stream()))
+  if any(l.get('momentum2') is not None for l in layers):
+    check(lib.rigl_prune_regrow_slots(arr, mom2, nl, C.byref(prm), _ptr(counts), _ptr(ws),
+                                      ws.numel(), _stream()))
+  else:
+    check(lib.rigl_prune_regrow(arr, nl, C.byref(prm), _ptr(counts), _ptr(ws),
+                                ws.numel(), _stream()))
   return counts
 
 
@@ -170,6 +180,10 @@ def prune_regrow_selections(layer, drop_fraction, grow_init_mode=_lib.GROW_ZEROS
     setattr(arr, key, t.data_ptr() if t is not None else None)
   _req(layer['mask_bits'], torch.int32, 'mask_bits')
   arr.mask_bits = layer['mask_bits'].data_ptr()
+  m2 = layer.get('momentum2')
+  _req(m2, torch.float32, 'momentum2', allow_none=True)
+  if m2 is not None and m2.numel() != n:
+    raise ValueError('momentum2 has %d elements, expected %d' % (m2.numel(), n))
   prm = PruneRegrowParams(float(drop_fraction), int(grow_init_mode), float(grow_init_div), int(momentum_reset_mode),
                           float(initial_acc_scale), int(bool(reinit_when_same)))
   words = n_mask_words(n)
@@ -180,9 +194,9 @@ def prune_regrow_selections(layer, drop_fraction, grow_init_mode=_lib.GROW_ZEROS
     out['idx1'] = torch.empty(n, dtype=torch.int32, device=dev)
     out['idx2'] = torch.empty(n, dtype=torch.int32, device=dev)
   ws = workspace(lib.rigl_prune_regrow_selections_workspace_bytes(n), dev, 'k2sel')
-  check(lib.rigl_prune_regrow_selections(C.byref(arr), C.byref(prm), _ptr(out['mask1_bits']), _ptr(out['mask2_bits']),
-                                         _ptr(out.get('idx1')), _ptr(out.get('idx2')), _ptr(out['counts']), _ptr(ws),
-                                         ws.numel(), _stream()))
+  check(lib.rigl_prune_regrow_selections_slots(C.byref(arr), _ptr(m2), C.byref(prm), _ptr(out['mask1_bits']),
+                                               _ptr(out['mask2_bits']), _ptr(out.get('idx1')), _ptr(out.get('idx2')),
+                                               _ptr(out['counts']), _ptr(ws), ws.numel(), _stream()))
   return out
 
 
@@ -239,6 +253,37 @@ def masked_sgd_momentum(w, grad, lr, momentum=None, mask_bits=None, mu=0.0,
       n, _ptr(w), _ptr(momentum), _ptr(grad), _ptr(mask_bits), float(lr),
       float(mu), float(weight_decay), float(grad_scale), int(bool(nesterov)),
       _ptr(w_shadow), _stream()))
+
+
+def masked_adam(w, grad, m, v, beta_powers, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, mask_bits=None,
+                weight_decay=0.0, grad_scale=1.0, w_shadow=None):
+  """K3-Adam (rigl_masked_adam): one TF ApplyAdam step on w / m / v in place; the bias correction is read from the
+  DEVICE tensor ``beta_powers`` (fp32 [2]), which ``adam_advance`` moves on once per step."""
+  _req(w, torch.float32, 'w')
+  _req(grad, torch.float32, 'grad')
+  _req(m, torch.float32, 'm')
+  _req(v, torch.float32, 'v')
+  _req(beta_powers, torch.float32, 'beta_powers')
+  _req(mask_bits, torch.int32, 'mask_bits', allow_none=True)
+  _req(w_shadow, torch.bfloat16, 'w_shadow', allow_none=True)
+  n = w.numel()
+  if grad.numel() != n or m.numel() != n or v.numel() != n or beta_powers.numel() != 2:
+    raise ValueError('size mismatch')
+  if mask_bits is not None and mask_bits.numel() < n_mask_words(n):
+    raise ValueError('mask_bits too small')
+  if w_shadow is not None and w_shadow.numel() != n:
+    raise ValueError('w_shadow size mismatch')
+  check(_lib.load().rigl_masked_adam(
+      n, _ptr(w), _ptr(m), _ptr(v), _ptr(grad), _ptr(mask_bits), _ptr(beta_powers), float(lr), float(beta1),
+      float(beta2), float(epsilon), float(weight_decay), float(grad_scale), _ptr(w_shadow), _stream()))
+
+
+def adam_advance(beta_powers, beta1=0.9, beta2=0.999):
+  """beta_powers *= (beta1, beta2) on the device (AdamOptimizer._finish)."""
+  _req(beta_powers, torch.float32, 'beta_powers')
+  if beta_powers.numel() != 2:
+    raise ValueError('beta_powers must hold 2 floats')
+  check(_lib.load().rigl_adam_advance(_ptr(beta_powers), float(beta1), float(beta2), _stream()))
 
 
 def pack_weights_batched(layers):
@@ -1140,5 +1185,5 @@ def prof_collect():
   """{kind: (milliseconds, launches)} accumulated since the last collect."""
   ms = (C.c_double * len(_lib.PROF_KINDS))()
   cnt = (C.c_int64 * len(_lib.PROF_KINDS))()
-  check(_lib.load().rigl_prof_collect(ms, cnt))
+  check(_lib.load().rigl_prof_collect_kinds(ms, cnt, len(_lib.PROF_KINDS)))
   return {k: (ms[i], cnt[i]) for i, k in enumerate(_lib.PROF_KINDS)}

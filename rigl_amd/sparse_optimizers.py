@@ -171,9 +171,9 @@ class SparseSETOptimizerBase(train.Optimizer):
     """:276-343 with explicit score tensors (same shape as the weights)."""
     lv = self._find_layer(mask, weights)
     req = dict(w=lv.weights.data.view(-1), mask_bits=lv.mask.bits,
-               momentum=self._slot_of(lv),
                score_drop=_flat_f32(score_drop, self.graph.device),
                score_grow=_flat_f32(score_grow, self.graph.device))
+    self._attach_slots(req, lv)
     self._attach_grow_values(req, lv)
     self._run_update([req], reinit_when_same=reinit_when_same)
     return mask
@@ -264,11 +264,21 @@ class SparseSETOptimizerBase(train.Optimizer):
         return l
     raise ValueError('no masked layer owns %r / %r' % (mask, weights))
 
-  def _slot_of(self, lv):
-    names = self._optimizer.get_slot_names()
-    if not names:
-      return None
-    return self._optimizer.get_slot(lv.weights, names[0]).view(-1)
+  def _slots_of(self, lv):
+    """The inner optimizer's slots of one layer, flat: [] / [momentum] / [m, v].  K2 resets both in-line (every slot
+    of a grown connection, :345-353 / :555-564); more than two cannot be expressed and raise rather than being
+    silently left stale."""
+    names = list(self._optimizer.get_slot_names())
+    if len(names) > 2:
+      raise NotImplementedError('the fused mask update resets at most two optimizer slots per weight; %s has %d (%s)'
+                                % (type(self._optimizer).__name__, len(names), names))
+    return [self._optimizer.get_slot(lv.weights, nm).view(-1) for nm in names]
+
+  def _attach_slots(self, req, lv):
+    slots = self._slots_of(lv)
+    req['momentum'] = slots[0] if slots else None
+    if len(slots) > 1:
+      req['momentum2'] = slots[1]
 
   def _prefetch_drop_noise(self, layers):
     """stateless_random_normal(shape, stddev, seed=[offset + hash(name + 'drop'), global_step]) of every layer
@@ -297,10 +307,10 @@ class SparseSETOptimizerBase(train.Optimizer):
     """SET: magnitude drop (+noise), uniform-random grow scores (:260-274)."""
     noise_std = self._noise_std if noise_std is None else noise_std
     req = dict(w=lv.weights.data.view(-1), mask_bits=lv.mask.bits,
-               momentum=self._slot_of(lv),
                drop_noise=self._drop_noise(lv, noise_std),
                score_grow=self._random_uniform(
                    lv.weights.shape, seed=self._seed(lv.weights, 'grow')).view(-1))
+    self._attach_slots(req, lv)
     self._attach_grow_values(req, lv)
     return req
 
@@ -415,8 +425,9 @@ class SparseRigLOptimizerBase(SparseSETOptimizerBase):
     if grad is None:
       grad = lv.weights.grad
     req = dict(w=lv.weights.data.view(-1), mask_bits=lv.mask.bits,
-               momentum=self._slot_of(lv), dense_grad=grad.view(-1),
+               dense_grad=grad.view(-1),
                drop_noise=self._drop_noise(lv, noise_std))
+    self._attach_slots(req, lv)
     self._attach_grow_values(req, lv)
     return req
 
@@ -474,9 +485,9 @@ class SparseStaticOptimizer(SparseSETOptimizer):
   def _layer_request(self, lv, noise_std=None):
     noise_std = self._noise_std if noise_std is None else noise_std
     req = dict(w=lv.weights.data.view(-1), mask_bits=lv.mask.bits,
-               momentum=self._slot_of(lv),
                drop_noise=self._drop_noise(lv, noise_std),
                score_grow=lv.mask.data.view(-1))            # :121
+    self._attach_slots(req, lv)
     self._attach_grow_values(req, lv)
     return req
 
@@ -533,9 +544,9 @@ class SparseMomentumOptimizer(SparseSETOptimizer):
   def _layer_request(self, lv, noise_std=None):
     noise_std = self._noise_std if noise_std is None else noise_std
     req = dict(w=lv.weights.data.view(-1), mask_bits=lv.mask.bits,
-               momentum=self._slot_of(lv),
                drop_noise=self._drop_noise(lv, noise_std),
                score_grow=self._ema[lv.weights.name].abs().contiguous().view(-1))
+    self._attach_slots(req, lv)
     self._attach_grow_values(req, lv)
     return req
 

@@ -1,11 +1,13 @@
 """Inner optimizers with the tf.train.Optimizer surface the reference wraps
 (``compute_gradients`` / ``apply_gradients`` / ``minimize`` / slots), executing
-on the fused HIP update kernel (K3, rigl_masked_sgd_momentum).
+on the fused HIP update kernels (K3, rigl_masked_sgd_momentum / rigl_masked_adam).
 
   tf.train.MomentumOptimizer(lr, momentum, use_nesterov=True)
       rigl/imagenet_resnet/imagenet_train_eval.py:360-361,
       rigl/cifar_resnet/resnet_train_eval.py:202-203, mnist_train_eval.py:263
   tf.train.GradientDescentOptimizer(lr)      rigl/sparse_optimizers_test.py:44
+  tf.train.AdamOptimizer(lr)                 imagenet_train_eval.py:355-358 (--use_adam),
+      mnist_train_eval.py:247-261 (--optimizer=adam)
 
 Eager twin of the TF1 graph API: ``compute_gradients(loss)`` runs the backward
 pass (the masked-layer autograd bridge deposits DENSE kernel gradients in the
@@ -131,18 +133,13 @@ class GradientDescentOptimizer(Optimizer):
       wd = wds.pop() if wds else 0.0
       if kind == V.KIND_MASKED and self.dense_masked_update:
         wd = 0.0                 # DNW: gradients are taken w.r.t. mask*W, which the l2 regulariser does not reach
-      ops.masked_sgd_momentum(
-          g.W[b:e], g.G[b:e], lr,
-          momentum=self._slot[b:e] if self._slot is not None else None,
-          mask_bits=(g.BITS[b // 32:e // 32]
-                     if kind == V.KIND_MASKED and not self.dense_masked_update else None),
-          mu=mu, weight_decay=wd, grad_scale=scale, nesterov=self._nesterov)
+      self._apply_range(b, e, (g.BITS[b // 32:e // 32]
+                               if kind == V.KIND_MASKED and not self.dense_masked_update else None),
+                        lr, mu, wd, scale)
     b, e = g.seg[V.KIND_OTHER]
     if e > b:
-      ops.masked_sgd_momentum(
-          g.W[b:e], g.G[b:e], lr,
-          momentum=self._slot[b:e] if self._slot is not None else None,
-          mu=mu, weight_decay=0.0, grad_scale=scale, nesterov=self._nesterov)
+      self._apply_range(b, e, None, lr, mu, 0.0, scale)
+    self._finish()
     g.shadows_dirty = True
     self._backward_done_for = None
     if global_step is not None:
@@ -157,12 +154,20 @@ class GradientDescentOptimizer(Optimizer):
         continue
       o, n = v.offset, v.numel
       n4 = (n + 3) // 4 * 4  # padding inside the 64-aligned slot is harmless
-      ops.masked_sgd_momentum(
-          g.W[o:o + n4], g.G[o:o + n4], lr,
-          momentum=self._slot[o:o + n4] if self._slot is not None else None,
-          mask_bits=(l.mask.bits if l.mask is not None and not self.dense_masked_update else None), mu=mu,
-          weight_decay=(0.0 if (kind == V.KIND_MASKED and self.dense_masked_update) else v.weight_decay), grad_scale=scale,
-          nesterov=self._nesterov)
+      self._apply_range(o, o + n4, (l.mask.bits if l.mask is not None and not self.dense_masked_update else None),
+                        lr, mu, (0.0 if (kind == V.KIND_MASKED and self.dense_masked_update) else v.weight_decay),
+                        scale)
+
+  def _apply_range(self, b, e, mask_bits, lr, mu, wd, scale):
+    """One update launch over arena elements [b, e) (K3)."""
+    g = self.graph
+    ops.masked_sgd_momentum(
+        g.W[b:e], g.G[b:e], lr,
+        momentum=self._slot[b:e] if self._slot is not None else None,
+        mask_bits=mask_bits, mu=mu, weight_decay=wd, grad_scale=scale, nesterov=self._nesterov)
+
+  def _finish(self):
+    """After the last segment of a step (tf.train.Optimizer._finish)."""
 
 
 class MomentumOptimizer(GradientDescentOptimizer):
@@ -193,6 +198,64 @@ class MomentumOptimizer(GradientDescentOptimizer):
     self.graph.finalize()
     self._ensure_slots()
     return self._slot[var.offset:var.offset + var.numel].view(var.shape)
+
+
+class AdamOptimizer(GradientDescentOptimizer):
+  """tf.train.AdamOptimizer (TF ApplyAdam, non-Nesterov) on K3-Adam (rigl_masked_adam):
+    alpha = (lr * sqrt(1 - beta2_power)) / (1 - beta1_power)
+    m += (g - m) * (1 - beta1);  v += (g*g - v) * (1 - beta2);  w -= (m * alpha) / (sqrt(v) + epsilon)
+  with g = mask * grad_scale * dense + wd * w as for the momentum path.  Masked-off weights are updated too (the
+  reference applies Adam to the raw variable).  Slots 'm' and 'v' are two flat arenas with the layout of W; the
+  beta powers are a device buffer (beta1_power, beta2_power) that starts at (beta1, beta2) and is multiplied by them
+  once per apply_gradients, after every variable is updated (_finish) -- mask-update iterations of RigL do not call
+  the inner apply and so do not advance it.  Used by imagenet_train_eval.py --use_adam (:214-215, 355-358) and
+  mnist_train_eval.py --optimizer=adam (:247-261)."""
+
+  def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8, use_locking=False, name='Adam',
+               graph=None, grad_sync=None):
+    super().__init__(learning_rate, use_locking, name, graph, grad_sync)
+    self._beta1 = float(beta1)
+    self._beta2 = float(beta2)
+    self._epsilon = float(epsilon)
+    self._slot_v = None            # second flat arena ('v'); self._slot is 'm'
+    self._beta_powers = None       # device fp32 [2]
+
+  def get_slot_names(self):
+    return ['m', 'v']              # TF sorts the slot names
+
+  def _ensure_slots(self):
+    g = self.graph
+    if self._slot is None or self._slot.numel() != g.W.numel():
+      if self._slot is not None:
+        raise RuntimeError('variables were added after the Adam slots were created')
+      self._slot = torch.zeros_like(g.W)
+      self._slot_v = torch.zeros_like(g.W)
+      self._beta_powers = torch.tensor([self._beta1, self._beta2], dtype=torch.float32, device=g.W.device)
+
+  def get_slot(self, var, name):
+    if name not in ('m', 'v'):
+      raise KeyError(name)
+    self.graph.finalize()
+    self._ensure_slots()
+    arena = self._slot if name == 'm' else self._slot_v
+    return arena[var.offset:var.offset + var.numel].view(var.shape)
+
+  def _get_beta_accumulators(self):
+    """Host copies (beta1_power, beta2_power) of the device accumulators."""
+    self.graph.finalize()
+    self._ensure_slots()
+    bp = self._beta_powers.cpu()
+    return bp[0].item(), bp[1].item()
+
+  def _apply_range(self, b, e, mask_bits, lr, mu, wd, scale):
+    del mu
+    g = self.graph
+    ops.masked_adam(g.W[b:e], g.G[b:e], self._slot[b:e], self._slot_v[b:e], self._beta_powers, lr,
+                    beta1=self._beta1, beta2=self._beta2, epsilon=self._epsilon, mask_bits=mask_bits,
+                    weight_decay=wd, grad_scale=scale)
+
+  def _finish(self):
+    ops.adam_advance(self._beta_powers, self._beta1, self._beta2)
 
 
 class GraphedStep:
