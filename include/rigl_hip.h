@@ -202,6 +202,41 @@ int rigl_topk_mask_batched(const RiglTopkLayer* layers /* host */,
                            int32_t n_layers, void* workspace,
                            size_t workspace_bytes, rigl_stream_t stream);
 
+/* Gradual magnitude pruning (Zhu & Gupta), the 'prune' training_method of
+ * rigl/mnist/mnist_train_eval.py:96-100, 320-337 and
+ * rigl/cifar_resnet/resnet_train_eval.py:85, 249-275, which run
+ * tf.contrib.model_pruning.  Replaces the mask update of TF 1.15
+ * contrib/model_pruning/python/pruning.py (Pruning._update_mask, weight
+ * magnitude, 1x1 blocks, no histogram / TPU path), per masked layer with n
+ * weights (raw kernel W, not mask*W) and a k the caller derived from the
+ * sparsity schedule (k = round_half_even(f32(n) * (1 - s_l))):
+ *   cur       = the k-th largest |W|  (top_k of every |W|, gather(values, k-1))
+ *   threshold = f32(cur * f32(1 - decay)) + f32(threshold * f32(decay))
+ *   mask      = |W| >= threshold      (every tie admitted: popcount >= k)
+ * Weights and optimizer slots are not touched.  The selection runs on K2's
+ * segmented radix select (all layers in the same launches) over the key
+ * bits(w) & 0x7fffffff, then one pass writes every bitmap (tail bits of the
+ * last word zero) and the new thresholds are stored.  No host sync.        */
+typedef struct RiglMagnitudePruneLayer {
+  int64_t n;            /* 1 <= n < 2^31 */
+  const float* w;       /* fp32 [n], read only */
+  uint32_t* mask_bits;  /* out, ceil(n/32) words */
+  float* threshold;     /* device fp32 [1]: in = the stored threshold, out = the new one */
+  int64_t k;            /* 1 <= k <= n (contrib's k == 0 fails in gather(values, -1)) */
+} RiglMagnitudePruneLayer;
+/* Workspace of rigl_magnitude_prune_batched: per-layer state only.         */
+size_t rigl_magnitude_prune_batched_workspace_bytes(int32_t n_layers);
+/* One call for all masked layers of a model.  threshold_decay = contrib's
+ * hparam (fp32 constants f32(decay) and f32(1 - decay) as TF forms them).
+ * out_counts (device, RIGL_MAGPRUNE_COUNTS_PER_LAYER * n_layers, nullable):
+ * per layer n, k, ones of the new mask, ones of the old mask.  Timed under
+ * profiler kind 9 (magnitude_prune).                                      */
+#define RIGL_MAGPRUNE_COUNTS_PER_LAYER 4
+int rigl_magnitude_prune_batched(const RiglMagnitudePruneLayer* layers /* host */,
+                                 int32_t n_layers, double threshold_decay,
+                                 int32_t* out_counts, void* workspace,
+                                 size_t workspace_bytes, rigl_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * K3: masked fused SGD / momentum update (+ bf16 shadow of mask*W).
  * Replaces: the TF ApplyMomentum / ApplyGradientDescent kernels behind
@@ -763,9 +798,10 @@ int rigl_eval_metrics(int32_t rows, int32_t classes, const rigl_bf16* logits,
 int rigl_prof_enable(int32_t on);
 int rigl_prof_collect(double* ms_per_kind /*[8]*/, int64_t* launches /*[8]*/);
 /* The same over the first n_kinds (<= RIGL_PROF_KINDS_ALL) families: kind
- * 8 = masked_adam (rigl_masked_adam and rigl_adam_advance).  rigl_prof_collect
- * keeps its eight-entry contract and drops kind 8's events.                 */
-#define RIGL_PROF_KINDS_ALL 9
+ * 8 = masked_adam (rigl_masked_adam and rigl_adam_advance), 9 =
+ * magnitude_prune (rigl_magnitude_prune_batched).  rigl_prof_collect keeps
+ * its eight-entry contract and drops the events of kinds 8 and up.          */
+#define RIGL_PROF_KINDS_ALL 10
 int rigl_prof_collect_kinds(double* ms_per_kind, int64_t* launches, int32_t n_kinds);
 /* The same events one by one, in launch order (instead of rigl_prof_collect,
  * which consumes them too): kind as above; tag = (h, w, cin, cout, kh, stride_h)

@@ -16,8 +16,9 @@ RIGL_ELAUNCH = -2
 RIGL_EWORKSPACE = -3
 RIGL_EUNSUPPORTED = -4
 COUNTS_PER_LAYER = 8
+MAGPRUNE_COUNTS_PER_LAYER = 4
 PROF_KINDS = ('conv_fwd', 'conv_dgrad', 'conv_wgrad', 'prune_regrow',
-              'sgd_momentum', 'pack_weights', 'conv_bwd', 'depthwise', 'masked_adam')
+              'sgd_momentum', 'pack_weights', 'conv_bwd', 'depthwise', 'masked_adam', 'magnitude_prune')
 
 GROW_ZEROS, GROW_GRAD_SCALE, GROW_GRAD_SIGN, GROW_EXPLICIT = 0, 1, 2, 3
 MOMRESET_ZEROS, MOMRESET_GRAD = 0, 1
@@ -46,6 +47,12 @@ class PruneRegrowParams(C.Structure):
 class TopkLayer(C.Structure):
   _fields_ = [('score', C.c_void_p), ('n', C.c_int64), ('n_keep', C.c_int64),
               ('mask_bits', C.c_void_p)]
+
+
+class MagnitudePruneLayer(C.Structure):
+  """RiglMagnitudePruneLayer: one masked tensor of rigl_magnitude_prune_batched."""
+  _fields_ = [('n', C.c_int64), ('w', C.c_void_p), ('mask_bits', C.c_void_p), ('threshold', C.c_void_p),
+              ('k', C.c_int64)]
 
 
 class PackLayer(C.Structure):
@@ -105,6 +112,8 @@ SIGNATURES = {
                                                      _P, _P, _P, _P, _SZ, _P]),
     'rigl_topk_mask': (C.c_int, [_P, _I64, _I64, _P, _P, _SZ, _P]),
     'rigl_topk_mask_batched': (C.c_int, [C.POINTER(TopkLayer), _I32, _P, _SZ, _P]),
+    'rigl_magnitude_prune_batched_workspace_bytes': (_SZ, [_I32]),
+    'rigl_magnitude_prune_batched': (C.c_int, [C.POINTER(MagnitudePruneLayer), _I32, C.c_double, _P, _P, _SZ, _P]),
     'rigl_masked_sgd_momentum': (C.c_int, [_I64, _P, _P, _P, _P, _F, _F, _F, _F,
                                            _I32, _P, _P]),
     'rigl_masked_adam': (C.c_int, [_I64, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P, _P]),

@@ -9,6 +9,8 @@
 // counts -> per-layer exclusive scan -> in-chunk scan).  All layers of a model
 // are processed by the same launches (segmented by a chunk table), so a whole
 // ResNet-50 update is 17 launches, not 54 x 17.
+// rigl_magnitude_prune_batched (contrib model_pruning's mask update) runs the same three digit passes on the key
+// bits(w) & 0x7fffffff of every weight, then one apply pass: its threshold admits every tie, so no tie passes.
 //
 // HBM-bound integer/compare work: 16 B/lane coalesced loads, wave64 shuffles to
 // assemble the 1-bit/weight bitmap, LDS histograms, no MFMA.
@@ -175,6 +177,43 @@ __device__ __forceinline__ void grow_scores(const LayerDev& L, const Pos& q, uin
   }
 }
 
+// ---- magnitude prune (rigl_magnitude_prune_batched) -------------------------------------------------------------------
+// Element s*BLOCK + threadIdx.x of a chunk belongs to lane threadIdx.x (s < MAG_PER): every load of a wave is 256
+// contiguous bytes, and the 64 lanes of a wave own 64 consecutive elements, i.e. two bitmap words (one __ballot).  Every
+// load of a chunk is issued, from an index clamped into the layer; lanes past n read a copy of an in-range value and are
+// masked out afterwards.  No alignment is assumed.
+constexpr int MAG_PER = SEGS * VEC;           // elements per lane per chunk
+template <typename T>
+__device__ __forceinline__ __attribute__((address_space(1))) T* as_global(T* p) {
+  return (__attribute__((address_space(1))) T*)p;
+}
+__device__ __forceinline__ int64_t mag_elem(uint32_t chunk_local, int s) {
+  return (int64_t)chunk_local * CHUNK + (int64_t)s * BLOCK + threadIdx.x;
+}
+// key = bits(w) & 0x7fffffff: the ordering of |w| as an unsigned integer, +0 and -0 equal, and the key IS |w|'s bits.
+__device__ __forceinline__ void mag_keys(const LayerDev& L, uint32_t chunk_local, uint32_t key[MAG_PER]) {
+  const auto* w = as_global(L.w);
+#pragma unroll
+  for (int s = 0; s < MAG_PER; ++s) key[s] = __float_as_uint(w[min(mag_elem(chunk_local, s), L.n - 1)]);
+#pragma unroll
+  for (int s = 0; s < MAG_PER; ++s) key[s] &= 0x7FFFFFFFu;
+}
+// Ones of the chunk's 128 bitmap words (threads 0..127, one word each; bits past n ignored).
+__device__ __forceinline__ uint32_t mag_chunk_ones(const LayerDev& L, uint32_t chunk_local) {
+  const int64_t n_words = (L.n + 31) >> 5;
+  const int64_t wi = (int64_t)chunk_local * (CHUNK / 32) + (threadIdx.x & (CHUNK / 32 - 1));
+  uint32_t word = as_global(L.mask)[min(wi, n_words - 1)];
+  if (wi == n_words - 1 && (L.n & 31)) word &= (1u << (L.n & 31)) - 1u;
+  return (threadIdx.x < CHUNK / 32 && wi < n_words) ? __popc(word) : 0u;
+}
+// The layer's threshold slot: the magnitude path reuses the selection kernels' layer table and carries its device fp32
+// threshold in `mom`, which it has no other use for.
+__device__ __forceinline__ float* mag_threshold_ptr(const LayerDev& L) { return L.mom; }
+// contrib _update_mask: smoothed = cur * (1 - decay) + threshold * decay, each product and the sum rounded to fp32.
+__device__ __forceinline__ float mag_smoothed(uint32_t cur_key, float old, float one_minus_decay, float decay) {
+  return __fadd_rn(__fmul_rn(__uint_as_float(cur_key), one_minus_decay), __fmul_rn(old, decay));
+}
+
 template <int P>
 __device__ __forceinline__ bool digit_of(uint32_t key, uint32_t prefix, uint32_t* bin) {
   if (P == 0) { *bin = key >> 21; return true; }
@@ -294,7 +333,7 @@ __device__ __forceinline__ void chunk_range(uint32_t total, uint32_t* c0, uint32
   *c1 = (uint32_t)((uint64_t)(blockIdx.x + 1) * total / gridDim.x);
 }
 
-template <int P>
+template <int P, bool MAG = false>
 __global__ __launch_bounds__(BLOCK) void k_drop_hist(const LayerDev* __restrict__ Ls, LayerState* __restrict__ St,
                                                      int n_layers, uint32_t total_chunks) {
   __shared__ uint32_t h[NB];
@@ -340,6 +379,19 @@ __global__ __launch_bounds__(BLOCK) void k_drop_hist(const LayerDev* __restrict_
     const SelState sel = St[li].d;
     if (P > 0 && sel.mode != 0u) continue;
     const uint32_t cl = c - L.chunk_begin;
+    if constexpr (MAG) {
+      // magnitude prune: key |W| of every entry; P == 0 also counts the old mask's ones
+      uint32_t key[MAG_PER];
+      mag_keys(L, cl, key);
+      if (P == 0) ones += mag_chunk_ones(L, cl);
+#pragma unroll
+      for (int s = 0; s < MAG_PER; ++s) {
+        uint32_t bin = 0u;
+        const bool in = digit_of<P>(key[s], sel.prefix, &bin) && mag_elem(cl, s) < L.n;
+        hist_add(h, in, bin);
+      }
+      continue;
+    }
 #pragma unroll
     for (int j = 0; j < SEGS; ++j) {
       Pos q = quad_pos(L.n, cl, j);
@@ -370,7 +422,7 @@ __global__ __launch_bounds__(BLOCK) void k_drop_hist(const LayerDev* __restrict_
 }
 
 // Per-layer digit scan: picks the bin holding the k-th largest key.
-template <int WHICH, int P>
+template <int WHICH, int P, bool MAG = false>
 __global__ __launch_bounds__(BLOCK) void k_scan(const LayerDev* __restrict__ Ls, LayerState* __restrict__ St,
                                                 Params prm) {
   __shared__ uint32_t sh[BLOCK];
@@ -404,7 +456,7 @@ __global__ __launch_bounds__(BLOCK) void k_scan(const LayerDev* __restrict__ Ls,
       sel.prefix = 0u;
       sel.ties = 0u;
       if (k <= 0) { sel.mode = 1u; sel.T = 0xFFFFFFFFu; sel.r = 0u; sel.k_rem = 0u; }
-      else if (k >= L.n) { sel.mode = 2u; sel.T = 0u; sel.r = (uint32_t)L.n; sel.k_rem = 0u; }
+      else if (!MAG && k >= L.n) { sel.mode = 2u; sel.T = 0u; sel.r = (uint32_t)L.n; sel.k_rem = 0u; }
       else { sel.mode = 0u; sel.k_rem = (uint32_t)k; }
     }
     s_mode = sel.mode;
@@ -821,6 +873,57 @@ __global__ void k_write_table(LayerBatch b, LayerDev* __restrict__ dst, int base
   if (i < count) dst[base + i] = b.l[i];
 }
 
+// Magnitude prune apply: mask = (|W| >= smoothed threshold) over one chunk per workgroup, the old threshold read from the
+// layer's slot (k_mag_finish stores the new one after this pass).  Counts the new ones per layer.
+__global__ __launch_bounds__(BLOCK) void k_mag_apply(const LayerDev* __restrict__ Ls, LayerState* __restrict__ St,
+                                                     int n_layers, float one_minus_decay, float decay) {
+  __shared__ uint32_t s_ones[BLOCK / 64];
+  const int li = find_layer(Ls, n_layers, blockIdx.x);
+  const LayerDev L = Ls[li];
+  LayerState& S = St[li];
+  const uint32_t cl = blockIdx.x - L.chunk_begin;
+  uint32_t key[MAG_PER];
+  mag_keys(L, cl, key);
+  const float thr = mag_smoothed(S.d.T, *as_global(mag_threshold_ptr(L)), one_minus_decay, decay);
+  const int64_t n_words = (L.n + 31) >> 5;
+  const int lane = threadIdx.x & 63;
+  uint32_t ones = 0u;
+#pragma unroll
+  for (int s = 0; s < MAG_PER; ++s) {
+    const int64_t e = mag_elem(cl, s);
+    const uint64_t b = __ballot(e < L.n && __uint_as_float(key[s]) >= thr);
+    const int64_t wi = ((e - lane) >> 5) + lane;            // lanes 0 and 1 store the wave's two words
+    if (lane < 2 && wi < n_words) as_global(L.mask)[wi] = (uint32_t)(b >> (32 * lane));
+    ones += (uint32_t)__popcll(b);
+  }
+  if (lane == 0) s_ones[threadIdx.x >> 6] = ones;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t o = 0u;
+#pragma unroll
+    for (int wv = 0; wv < BLOCK / 64; ++wv) o += s_ones[wv];
+    if (o) atomicAdd(&S.n_new_ones, o);
+  }
+}
+
+// One lane per layer: stores the smoothed threshold; optional counts (n, k, new ones, old ones).
+__global__ void k_mag_finish(const LayerDev* __restrict__ Ls, const LayerState* __restrict__ St, int n_layers,
+                             float one_minus_decay, float decay, int32_t* __restrict__ out) {
+  const int l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= n_layers) return;
+  const LayerDev& L = Ls[l];
+  const LayerState& S = St[l];
+  float* thr = mag_threshold_ptr(L);
+  *thr = mag_smoothed(S.d.T, *thr, one_minus_decay, decay);
+  if (out) {
+    int32_t* o = out + l * RIGL_MAGPRUNE_COUNTS_PER_LAYER;
+    o[0] = (int32_t)L.n;
+    o[1] = (int32_t)L.fixed_k;
+    o[2] = (int32_t)S.n_new_ones;
+    o[3] = (int32_t)S.n_ones;
+  }
+}
+
 // ------------------------------------------------------------------ host side
 struct Layout {
   size_t off_layers, off_state, off_tiecnt, off_tieoff, off_mask1, total;
@@ -940,6 +1043,74 @@ static int run(const RiglPruneRegrowLayer* layers, int n_layers, const int64_t* 
   if (out_counts)
     hipLaunchKernelGGL(k_counts, dim3((n_layers + 63) / 64), dim3(64), 0, stream, dS, n_layers, out_counts);
   RIGL_CHECK_LAUNCH("prune_regrow");
+  return RIGL_OK;
+}
+
+// Magnitude prune: the layer table and the per-layer selection state, nothing per element.
+struct MagLayout { size_t off_layers, off_state, total; };
+static MagLayout mag_layout(int n_layers) {
+  MagLayout lo;
+  size_t off = 0;
+  lo.off_layers = off; off = align_up(off + sizeof(LayerDev) * (size_t)n_layers, 256);
+  lo.off_state = off;  off = align_up(off + sizeof(LayerState) * (size_t)n_layers, 256);
+  lo.total = off;
+  return lo;
+}
+
+static int run_mag(const RiglMagnitudePruneLayer* layers, int n_layers, double threshold_decay, int32_t* out_counts,
+                   void* ws, size_t ws_bytes, hipStream_t stream) {
+  std::vector<LayerDev> hL(n_layers);
+  uint32_t chunk = 0;
+  for (int i = 0; i < n_layers; ++i) {
+    const RiglMagnitudePruneLayer& l = layers[i];
+    if (l.n <= 0 || l.n >= (int64_t(1) << 31))
+      return fail(RIGL_EINVAL, "magnitude_prune: layer %d: n=%lld out of range", i, (long long)l.n);
+    if (l.k < 1 || l.k > l.n)
+      return fail(RIGL_EINVAL, "magnitude_prune: layer %d: k=%lld not in [1, n=%lld]", i, (long long)l.k, (long long)l.n);
+    if (!l.w || !l.mask_bits || !l.threshold)
+      return fail(RIGL_EINVAL, "magnitude_prune: layer %d: w, mask_bits and threshold are required", i);
+    if ((chunk + (uint64_t)ceil_div64(l.n, CHUNK)) >> 32)
+      return fail(RIGL_EINVAL, "magnitude_prune: more than 2^32 chunks");
+    LayerDev d = {};
+    d.n = l.n;
+    d.w = const_cast<float*>(l.w);      // read only
+    d.mom = l.threshold;                // mag_threshold_ptr
+    d.mask = l.mask_bits;
+    d.chunk_begin = chunk;
+    d.n_chunks = (uint32_t)ceil_div64(l.n, CHUNK);
+    d.fixed_k = l.k;
+    chunk += d.n_chunks;
+    hL[i] = d;
+  }
+  const MagLayout lo = mag_layout(n_layers);
+  if (!ws || ws_bytes < lo.total) return fail(RIGL_EWORKSPACE, "magnitude_prune: workspace %zu < required %zu", ws_bytes, lo.total);
+  char* base = static_cast<char*>(ws);
+  LayerDev* dL = reinterpret_cast<LayerDev*>(base + lo.off_layers);
+  LayerState* dS = reinterpret_cast<LayerState*>(base + lo.off_state);
+  // TF: threshold * decay and cur * (1 - decay) take the Python floats as fp32 constants
+  const float decay = (float)threshold_decay, one_minus_decay = (float)(1.0 - threshold_decay);
+  const uint32_t C = chunk;
+  ProfScope prof(PROF_MAGPRUNE, stream);
+  for (int b = 0; b < n_layers; b += TABLE_BATCH) {
+    LayerBatch hb;
+    const int cnt = n_layers - b < TABLE_BATCH ? n_layers - b : TABLE_BATCH;
+    for (int i = 0; i < cnt; ++i) hb.l[i] = hL[b + i];
+    hipLaunchKernelGGL(k_write_table, dim3(1), dim3(TABLE_BATCH), 0, stream, hb, dL, b, cnt);
+  }
+  constexpr uint32_t hist_wgs = 1536, refine_wgs = 2048;     // rigl_prune_regrow's defaults for the same passes
+  const uint32_t HG = C < hist_wgs ? C : hist_wgs;
+  const uint32_t HR = C < refine_wgs ? C : refine_wgs;
+  hipLaunchKernelGGL(k_init_state, dim3(n_layers), dim3(256), 0, stream, dS, n_layers);
+  hipLaunchKernelGGL((k_drop_hist<0, true>), dim3(HG), dim3(BLOCK), 0, stream, dL, dS, n_layers, C);
+  hipLaunchKernelGGL((k_scan<0, 0, true>), dim3(n_layers), dim3(BLOCK), 0, stream, dL, dS, Params{});
+  hipLaunchKernelGGL((k_drop_hist<1, true>), dim3(HR), dim3(BLOCK), 0, stream, dL, dS, n_layers, C);
+  hipLaunchKernelGGL((k_scan<0, 1, true>), dim3(n_layers), dim3(BLOCK), 0, stream, dL, dS, Params{});
+  hipLaunchKernelGGL((k_drop_hist<2, true>), dim3(HR), dim3(BLOCK), 0, stream, dL, dS, n_layers, C);
+  hipLaunchKernelGGL((k_scan<0, 2, true>), dim3(n_layers), dim3(BLOCK), 0, stream, dL, dS, Params{});
+  hipLaunchKernelGGL(k_mag_apply, dim3(C), dim3(BLOCK), 0, stream, dL, dS, n_layers, one_minus_decay, decay);
+  hipLaunchKernelGGL(k_mag_finish, dim3((n_layers + 63) / 64), dim3(64), 0, stream, dL, dS, n_layers, one_minus_decay,
+                     decay, out_counts);
+  RIGL_CHECK_LAUNCH("rigl_magnitude_prune_batched");
   return RIGL_OK;
 }
 
@@ -1152,6 +1323,17 @@ int rigl_topk_mask(const float* score, int64_t n, int64_t n_keep, uint32_t* mask
   rigl::k2::Params p = {};
   uint32_t* ov = mask_bits;
   return rigl::k2::run(&l, 1, &n_keep, p, false, &ov, nullptr, workspace, workspace_bytes, rigl::as_stream(stream));
+}
+
+size_t rigl_magnitude_prune_batched_workspace_bytes(int32_t n_layers) {
+  return n_layers > 0 ? rigl::k2::mag_layout(n_layers).total : 0;
+}
+
+int rigl_magnitude_prune_batched(const RiglMagnitudePruneLayer* layers, int32_t n_layers, double threshold_decay,
+                                 int32_t* out_counts, void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
+  if (n_layers < 0 || (n_layers > 0 && !layers)) return rigl::fail(RIGL_EINVAL, "rigl_magnitude_prune_batched: bad arguments");
+  if (n_layers == 0) return RIGL_OK;
+  return rigl::k2::run_mag(layers, n_layers, threshold_decay, out_counts, workspace, workspace_bytes, rigl::as_stream(stream));
 }
 
 }  // extern "C"

@@ -235,6 +235,42 @@ def topk_mask_batched(items):
   check(lib.rigl_topk_mask_batched(arr, nl, _ptr(ws), ws.numel(), _stream()))
 
 
+def magnitude_prune_batched(items, threshold_decay=0.0, counts=None):
+  """contrib model_pruning's mask update (rigl_magnitude_prune_batched) for many tensors in one call.
+
+  items: list of (w fp32, mask_bits int32, threshold fp32 [1] device tensor, k) -- per tensor, the k-th largest |w|
+  smoothed with the stored threshold (thr = cur * (1 - threshold_decay) + thr * threshold_decay, fp32) becomes the new
+  threshold, and mask = |w| >= thr.  ``w`` is only read.  ``counts`` (optional int32 [len(items), 4] device tensor)
+  receives n, k, new ones, old ones per tensor.  No host sync."""
+  nl = len(items)
+  if nl == 0:
+    return counts
+  lib = _lib.load()
+  arr = (_lib.MagnitudePruneLayer * nl)()
+  for i, (w, bits, thr, k) in enumerate(items):
+    _req(w, torch.float32, 'w')
+    _req(bits, torch.int32, 'mask_bits')
+    _req(thr, torch.float32, 'threshold')
+    n = w.numel()
+    if bits.numel() < n_mask_words(n):
+      raise ValueError('mask_bits too small')
+    if thr.numel() != 1:
+      raise ValueError('threshold must hold one float')
+    arr[i].n = n
+    arr[i].w = w.data_ptr()
+    arr[i].mask_bits = bits.data_ptr()
+    arr[i].threshold = thr.data_ptr()
+    arr[i].k = int(k)
+  if counts is not None:
+    _req(counts, torch.int32, 'counts')
+    if counts.numel() < nl * _lib.MAGPRUNE_COUNTS_PER_LAYER:
+      raise ValueError('counts too small')
+  ws = workspace(lib.rigl_magnitude_prune_batched_workspace_bytes(nl), items[0][0].device, 'magprune')
+  check(lib.rigl_magnitude_prune_batched(arr, nl, float(threshold_decay), _ptr(counts), _ptr(ws), ws.numel(),
+                                         _stream()))
+  return counts
+
+
 # ----------------------------------------------------------------------------
 # K3
 # ----------------------------------------------------------------------------

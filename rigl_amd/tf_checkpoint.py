@@ -318,6 +318,10 @@ def variable_map(graph):
     if hasattr(mod, 'moving_mean') and hasattr(mod, 'moving_variance'):
       out[scope + '/moving_mean'] = _Buffer(mod.moving_mean)
       out[scope + '/moving_variance'] = _Buffer(mod.moving_variance)
+  state = getattr(graph, 'pruning_state', None)      # contrib's thresholds + step, once a pruning.Pruning exists
+  if state is not None:
+    for name, t in state.variable_items().items():
+      out[name] = _Buffer(t)
   return out
 
 
@@ -371,7 +375,8 @@ def load_into_graph(prefix, graph, param_suffixes=None, name_map=None, strict=Fa
     else:
       import torch  # pylint: disable=import-outside-toplevel
       with torch.no_grad():
-        obj.data.copy_(torch.from_numpy(arr.astype(np.float32)).to(obj.data.device))
+        src = arr.astype(np.int32 if obj.data.dtype == torch.int32 else np.float32)
+        obj.data.copy_(torch.from_numpy(src).to(obj.data.device))
     loaded.append(gname)
   graph.shadows_dirty = True
   return loaded
@@ -392,7 +397,8 @@ def save_graph(prefix, graph, extra=None):
     if hasattr(obj, 'bits'):
       tensors[name] = obj.numpy().astype(np.float32)
     else:
-      tensors[name] = obj.data.detach().cpu().numpy().astype(np.float32)
+      arr = obj.data.detach().cpu().numpy()
+      tensors[name] = arr if arr.dtype == np.int32 else arr.astype(np.float32)
   tensors.update(extra or {})
   write_bundle(prefix, tensors)
   return sorted(tensors)
