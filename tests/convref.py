@@ -43,6 +43,34 @@ def conv_fp64(x, w_hwio, dy, stride, pt, pl, ho, wo, want=('y', 'dx', 'dw')):
   return out
 
 
+def depthwise_fp64(x, w, dy, stride, pt, pl, ho, wo, want=('y', 'dx', 'dw')):
+  """Depthwise (channel multiplier 1) twin of conv_fp64: one elementwise product per filter tap on padded / strided
+  slices, autograd for dX and dW.  x [N,H,W,C], w [kh,kw,C] or [kh,kw,C,1], dy [N,Ho,Wo,C] (any float dtype, any
+  device) -> dict of fp64 tensors y [N,Ho,Wo,C], dx [N,H,W,C], dw [kh,kw,C]."""
+  N, H, W, C = x.shape
+  kh, kw = w.shape[0], w.shape[1]
+  sh, sw = (stride, stride) if isinstance(stride, int) else stride
+  pb = max((ho - 1) * sh + kh - H - pt, 0)
+  pr = max((wo - 1) * sw + kw - W - pl, 0)
+  need_grad = ('dx' in want) or ('dw' in want)
+  xd = x.double().detach().requires_grad_(need_grad and 'dx' in want)
+  wd = w.double().detach().reshape(kh, kw, C).requires_grad_(need_grad and 'dw' in want)
+  xp = F.pad(xd, (0, 0, pl, pr, pt, pb))
+  y = None
+  for r in range(kh):
+    for s in range(kw):
+      t = xp[:, r:r + (ho - 1) * sh + 1:sh, s:s + (wo - 1) * sw + 1:sw, :] * wd[r, s]
+      y = t if y is None else y + t
+  out = {'y': y.detach()}
+  if need_grad:
+    y.backward(dy.double())
+    if 'dx' in want:
+      out['dx'] = xd.grad
+    if 'dw' in want:
+      out['dw'] = wd.grad
+  return out
+
+
 def check_close(name, got, ref, absref, rel=1e-5, out_ulp=0.0):
   """|got - ref| <= out_ulp * |ref| + rel * absref  elementwise; raises with the worst offenders."""
   got, ref, absref = got.double(), ref.double(), absref.double()

@@ -11,6 +11,7 @@ which the library reads once per process, can be chosen per invocation:
   python tests/k1_check.py --set bs            # the channel-sliced single-pass 1x1 backward (bwdslice.hpp): 1 .. 32 slices, ragged tiles
   python tests/k1_check.py --set c3            # the slab-resident 3x3 kernels (64 -> 64 channels): tile heights, widths, partial tiles
   python tests/k1_check.py --set resnet50 --batch 128     # the 23 distinct ResNet-50 layer shapes at the benchmarked batch
+  python tests/k1_check.py --set mobilenet_v1 --batch 128 # MobileNet-v1's stem, 9 distinct pointwise layers and final_dense
 
 Prints one line per case and a final JSON line {"ok": true, "cases": n, "worst": ratio}; exit code 1 on a mismatch.
 Test infrastructure: the pytest files call it in a subprocess.
@@ -160,6 +161,23 @@ def resnet50_shapes(batch):
   return out
 
 
+def mobilenet_v1_shapes(batch):
+  """MobileNet-v1 at 224 x 224 (mobilenetv1_model.py:251-342): the 3x3 / 2 stem (fixed padding 1 / 1 + VALID, 3 -> 32),
+  the distinct pointwise 1x1 layers of workloads/shapes.MOBILENET_V1_BLOCKS (the depthwise convs have kernels of their own,
+  tests/test_k3_k1_gpu.py), and final_dense as the 1x1 conv it runs as (1024 -> 1000 over the batch rows)."""
+  from rigl_amd.workloads import shapes
+  out = [(batch, 224, 224, 3, 32, 3, 2, 1, 1, 112, 112)]
+  cin, hw = 32, 112
+  for f, stride in shapes.MOBILENET_V1_BLOCKS:
+    hw = (hw - 1) // stride + 1
+    c = (batch, hw, hw, cin, f, 1, 1, 0, 0, hw, hw)
+    if c not in out:
+      out.append(c)
+    cin = f
+  out.append((batch, 1, 1, 1024, 1000, 1, 1, 0, 0, 1, 1))
+  return out
+
+
 def run_case(case, seed, check_bwd_call=True, check_stats=True):
   from rigl_amd import ops
   N, H, W, Cin, Cout, k, stride, pt, pl, Ho, Wo = case
@@ -304,11 +322,13 @@ def run_case(case, seed, check_bwd_call=True, check_stats=True):
 
 def main():
   ap = argparse.ArgumentParser()
-  ap.add_argument('--set', default='small', choices=['small', 'pp', 'stem', 'c3', 'rs', 'bs', 'resnet50'])
+  ap.add_argument('--set', default='small', choices=['small', 'pp', 'stem', 'c3', 'rs', 'bs', 'resnet50', 'mobilenet_v1'])
   ap.add_argument('--batch', type=int, default=128)
   ap.add_argument('--only', type=int, default=-1)
   a = ap.parse_args()
-  cases = {'small': SMALL_CASES, 'pp': PP_CASES, 'stem': STEM_CASES, 'c3': C3_CASES, 'rs': RS_CASES, 'bs': BS_CASES}.get(a.set) or resnet50_shapes(a.batch)
+  cases = {'small': SMALL_CASES, 'pp': PP_CASES, 'stem': STEM_CASES, 'c3': C3_CASES, 'rs': RS_CASES, 'bs': BS_CASES}.get(a.set)
+  if cases is None:
+    cases = mobilenet_v1_shapes(a.batch) if a.set == 'mobilenet_v1' else resnet50_shapes(a.batch)
   worst, n = 0.0, 0
   for i, c in enumerate(cases):
     if a.only >= 0 and i != a.only:

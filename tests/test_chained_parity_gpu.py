@@ -51,7 +51,7 @@ class Recorder:
   """Stock-op network pieces in fp64 (NCHW) that remember what each node saw."""
 
   def __init__(self):
-    self.convs, self.bns = [], []
+    self.convs, self.bns, self.dws = [], [], []
 
   def conv(self, name, x, w_hwio_f32, k, stride, pads):
     """pads = (top, left, bottom, right).  Returns the bf16-rounded output."""
@@ -63,6 +63,19 @@ class Recorder:
     y_raw = F.conv2d(F.pad(xi, (pl, pr, pt, pb)), w.permute(3, 2, 0, 1), stride=stride)
     y_raw.retain_grad()                              # its .grad is the bf16-rounded gradient the conv's backward consumes
     self.convs.append(dict(name=name, x=xi, w=w, w32=w_hwio_f32, y=y_raw, k=k, stride=stride, pads=pads))
+    return rnd(y_raw)
+
+  def depthwise(self, name, x, w_hwc_f32, stride, pads):
+    """A grouped (channel multiplier 1) conv; the kernels read the fp32 weights [kh,kw,C] as they are.  pads = (top, left,
+    bottom, right).  Returns the bf16-rounded output."""
+    xi = (x * 1.0)
+    if xi.requires_grad:
+      xi.retain_grad()
+    w = w_hwc_f32.double().clone().requires_grad_(True)
+    pt, pl, pb, pr = pads
+    y_raw = F.conv2d(F.pad(xi, (pl, pr, pt, pb)), w.permute(2, 0, 1).unsqueeze(1), stride=stride, groups=w.shape[-1])
+    y_raw.retain_grad()
+    self.dws.append(dict(name=name, x=xi, w=w, w32=w_hwc_f32, y=y_raw, stride=stride, pads=pads))
     return rnd(y_raw)
 
   def bn(self, name, x, gamma, beta, relu, residual=None):
@@ -125,8 +138,15 @@ def check_conv_node(nd):
   return worst
 
 
-def check_bn_node(nd):
-  """The HIP batch norm (+ residual)(+ ReLU) forward and backward on the reference's tensors."""
+def check_bn_node(nd, sum_terms=False):
+  """The HIP batch norm (+ residual)(+ ReLU) forward and backward on the reference's tensors.
+
+  ``sum_terms``: dX = a (dz - dbeta / M - xhat dgamma / M) is held to its bound twice instead of once -- against the same
+  formula evaluated with the kernel's own dbeta / dgamma (each held to its fp32 bound just before), with the bound below
+  (the apply pass alone), and against the fp64 reference with the magnitudes of the SUMMED terms, sum|dz| / M and
+  |xhat| sum|dz xhat| / M, in place of |dbeta| / M and |xhat dgamma| / M (fp32 sums to 1e-5 of sum|terms|, as above).
+  For long channels whose sums cancel (MobileNet-v1, 1.6 M rows: |dbeta| ~ 1e-5 sum|dz|) no fp32 reduction of dbeta
+  is within 1e-5 |dbeta|, so the single bound on the reference's own sums would hold the kernel to more than fp32."""
   from rigl_amd import ops
   x = _nhwc_bf16(nd['x'])
   res = _nhwc_bf16(nd['res']) if nd['res'] is not None else None
@@ -177,6 +197,13 @@ def check_bn_node(nd):
   del bits
   worst = max(worst, convref.check_close(nd['name'] + ' dbeta', db, dbeta, dz.abs().sum(0), 1e-5))
   worst = max(worst, convref.check_close(nd['name'] + ' dgamma', dg, dgamma, (dz * xhat).abs().sum(0), 1e-5))
+  if sum_terms:
+    dbk, dgk = db.double(), dg.double()
+    dx_k = a * (dz - dbk / M - xhat * dgk / M)
+    mag_k = a.abs() * (dz.abs() + dbk.abs() / M + xhat.abs() * dgk.abs() / M)
+    worst = max(worst, convref.check_close(nd['name'] + ' dx (kernel sums)', dx_hip.reshape(M, C), dx_k, mag_k, 1e-5, 2.0 ** -8))
+    del dx_k, mag_k
+    dx_mag = a.abs() * (dz.abs() + dz.abs().sum(0) / M + xhat.abs() * (dz * xhat).abs().sum(0) / M)
   worst = max(worst, convref.check_close(nd['name'] + ' dx', dx_hip.reshape(M, C), dx_ref, dx_mag, 1e-5, 2.0 ** -8))
   if res is not None:
     assert torch.equal(dres.reshape(M, C).double(), dz), nd['name'] + ': the residual gradient is the masked gradient, exactly'
@@ -306,6 +333,14 @@ def check_stats_feed(cv, bn):
   d = ops.conv_desc(N, H, W, Cin, Cout, k, k, s, pt, pl, Ho, Wo)
   y, part = ops.conv_fwd(d, x, ohwi, stats=True)
   assert part is not None and part.shape[0] == d._stats_parts
+  _check_bn_on_partials(cv['name'], bn, y, part)
+
+
+def _check_bn_on_partials(src, bn, y, part):
+  """rigl_bn_fwd_stats on a producer's bf16 output ``y`` with that producer's partials against the same batch norm with its
+  own statistics pass over ``y``."""
+  from rigl_amd import ops
+  Cout = y.shape[-1]
   gamma, beta = bn['gamma'].float().contiguous(), bn['beta'].float().contiguous()
   relu = bn['relu'] and bn['res'] is None
   outs = []
@@ -317,7 +352,7 @@ def check_stats_feed(cv, bn):
   for a, b, what in ((s0[0], s1[0], 'mean'), (s0[1], s1[1], 'invstd'), (s0[2], s1[2], 'scale'), (s0[3], s1[3], 'shift'),
                      (rm0, rm1, 'moving mean'), (rv0, rv1, 'moving variance')):
     tol = 1e-5 * float(a.abs().max()) + 1e-7
-    assert float((a - b).abs().max()) <= tol, '%s -> %s: %s from the conv epilogue partials' % (cv['name'], bn['name'], what)
+    assert float((a - b).abs().max()) <= tol, '%s -> %s: %s from the epilogue partials' % (src, bn['name'], what)
   diff = (y0.float() - y1.float()).abs()
   assert float((diff / (y0.float().abs() * 2.0 ** -7 + 1e-6)).max()) <= 1.0, 'y differs by more than one bf16 ulp'
   assert float((diff > 0).float().mean()) <= 0.01
@@ -366,4 +401,119 @@ def test_resnet50_group1_bottlenecks_every_node_on_the_reference_tensors():
   for ci, bi in pairs:
     check_stats_feed(rec.convs[ci], rec.bns[bi])
   print('resnet50 group-1 chained: %d conv + %d batch-norm nodes, worst error / bound %.3f' % (len(rec.convs), len(rec.bns), worst))
+  assert worst <= 1.0
+
+
+def _dw_desc(nd):
+  from rigl_amd import ops
+  N, C, H, W = nd['x'].shape
+  Ho, Wo = nd['y'].shape[2], nd['y'].shape[3]
+  return ops.conv_desc(N, H, W, C, C, 3, 3, nd['stride'], nd['pads'][0], nd['pads'][1], Ho, Wo)
+
+
+def check_dw_node(nd):
+  """The HIP depthwise forward / dgrad / wgrad on the reference's tensors against tests/convref.py's depthwise_fp64, and that
+  reference against the recorded graph (grouped F.conv2d and its autograd) to 1e-9."""
+  from rigl_amd import ops
+  x = _nhwc_bf16(nd['x'])
+  dy = _nhwc_bf16(nd['y'].grad)
+  assert torch.equal(dy.double(), nd['y'].grad.detach().permute(0, 2, 3, 1)), 'the recorded gradient is not bf16-valued'
+  _, Ho, Wo, _ = dy.shape
+  s, pt, pl = nd['stride'], nd['pads'][0], nd['pads'][1]
+  w = nd['w32'].contiguous()
+  wd = w.reshape(-1)
+  d = _dw_desc(nd)
+  ref = convref.depthwise_fp64(x, w, dy, s, pt, pl, Ho, Wo)
+  ab = convref.depthwise_fp64(x.abs(), w.abs(), dy.abs(), s, pt, pl, Ho, Wo)
+  assert float((ref['y'] - nd['y'].detach().permute(0, 2, 3, 1)).abs().max()) <= 1e-9 * float(ab['y'].max() + 1e-30)
+  assert float((ref['dx'] - nd['x'].grad.detach().permute(0, 2, 3, 1)).abs().max()) <= 1e-9 * float(ab['dx'].max() + 1e-30)
+  assert float((ref['dw'] - nd['w'].grad).abs().max()) <= 1e-9 * float(ab['dw'].max() + 1e-30)
+  y = ops.depthwise_fwd(d, x, wd)
+  worst = convref.check_close(nd['name'] + ' fwd', y, ref['y'], ab['y'], 1e-5, 2.0 ** -8)
+  dx = ops.depthwise_dgrad(d, dy, wd)
+  worst = max(worst, convref.check_close(nd['name'] + ' dgrad', dx, ref['dx'], ab['dx'], 1e-5, 2.0 ** -8))
+  dw = torch.empty(wd.numel(), dtype=torch.float32, device=DEV)
+  ops.depthwise_wgrad(d, x, dy, dw)
+  worst = max(worst, convref.check_close(nd['name'] + ' wgrad', dw, ref['dw'].reshape(-1), ab['dw'].reshape(-1), 1e-5))
+  return worst
+
+
+def check_dw_stats_feed(dw, bn):
+  """check_stats_feed for the depthwise forward: its statistics partials (rigl_depthwise_conv2d_fwd_stats) feeding bn_a."""
+  from rigl_amd import ops
+  x = _nhwc_bf16(dw['x'])
+  y, part = ops.depthwise_fwd(_dw_desc(dw), x, dw['w32'].contiguous().reshape(-1), stats=True)
+  assert part is not None, dw['name'] + ': no statistics epilogue'
+  _check_bn_on_partials(dw['name'], bn, y, part)
+
+
+def _record_mobilenet_v1(batch, dev):
+  """MobileNet-v1 of BASELINE config 5 (bench.py's model, seed and uniform 90 % masks on the pointwise convs and
+  final_dense; stem and depthwise convs dense) as a recorded fp64 stock-op graph at 224 x 224, with random batch-norm
+  affine parameters, backpropagated from the cross-entropy of its logits.  Returns (recorder, statistics feeds)."""
+  from rigl_amd import sparse_utils, variables as V
+  from rigl_amd.workloads import mobilenet_v1
+  g = V.reset_default_graph(dev)
+  model = mobilenet_v1.MobileNetV1(g, seed=0)
+  np.random.seed(0)
+  sparse_utils.get_mask_init_fn(g.get_masks(), 'random', 0.9, {})()
+  gen = torch.Generator(device=dev).manual_seed(5)
+  bns = [model.stem_bn] + [b for blk in model.blocks for b in (blk[1], blk[3])]
+  for bn in bns:
+    c = bn.gamma.data.numel()
+    bn.gamma.data.copy_(1.0 + 0.2 * torch.randn(c, generator=gen, device=dev))
+    bn.beta.data.copy_(0.1 * torch.randn(c, generator=gen, device=dev))
+  images, labels = mobilenet_v1.synthetic_batch(batch, dev)
+  rec = Recorder()
+  feeds = []
+
+  def w_of(layer):
+    w = layer.weights.data.float()
+    if layer.mask is not None:
+      w = w * layer.mask.data.float().reshape(w.shape)
+    return w.contiguous()
+
+  def bn_relu(bn, name, x):
+    return rec.bn(name, x, bn.gamma.data, bn.beta.data, True)
+
+  # fixed padding 1 / 1 + VALID for the 3x3 stem and the stride-2 depthwise convs, SAME (also 1 / 1) at stride 1
+  net = rec.conv('initial_conv', images.double().permute(0, 3, 1, 2), w_of(model.stem), 3, 2, (1, 1, 1, 1))
+  net = bn_relu(model.stem_bn, 'initial_bn', net)
+  feeds.append(('conv', len(rec.convs) - 1, len(rec.bns) - 1))
+  for i, (dw, bn_a, pw, bn_b) in enumerate(model.blocks):
+    net = rec.depthwise('depthwise_nxn_%d' % i, net, dw.weights.data.float().reshape(3, 3, -1), dw.stride, (1, 1, 1, 1))
+    net = bn_relu(bn_a, 'depthwise_bn_%d' % i, net)
+    feeds.append(('dw', len(rec.dws) - 1, len(rec.bns) - 1))
+    net = rec.conv('contraction_1x1_%d' % i, net, w_of(pw), 1, 1, (0, 0, 0, 0))
+    net = bn_relu(bn_b, 'contraction_bn_%d' % i, net)
+    feeds.append(('conv', len(rec.convs) - 1, len(rec.bns) - 1))
+  feat = rnd(net.mean(dim=(2, 3)))
+  logits = rec.conv('final_dense', feat[:, :, None, None], w_of(model.fc).reshape(1, 1, 1024, -1), 1, 1, (0, 0, 0, 0))
+  logits = rnd(logits[:, :, 0, 0] + model.fc.bias.data.double())
+  F.cross_entropy(logits, labels).backward()
+  return rec, feeds
+
+
+def test_mobilenet_v1_every_node_on_the_reference_tensors():
+  """MobileNet-v1 (BASELINE config 5) at the benchmarked batch of 128 and 224 x 224, unsplit: kernel selection depends on
+  the row counts, so the small-batch config test does not run these kernels.  Every conv node (the 3x3 / 2 stem on the
+  tiny-C_in path, the 13 pointwise 1x1 convs, final_dense as a 1024 -> 1000 1x1 conv: 15), every depthwise node (13) and
+  every batch-norm node (27, C = 32 over 1.6 M rows included) on the reference's tensors, and every statistics feed
+  (stem -> initial_bn, depthwise -> bn_a, pointwise -> bn_b: 27) into the real batch norm."""
+  rec, feeds = _record_mobilenet_v1(128, DEV)
+  assert len(rec.convs) == 15 and len(rec.dws) == 13 and len(rec.bns) == 27 and len(feeds) == 27
+  worst = 0.0
+  for nd in rec.convs:
+    worst = max(worst, check_conv_node(nd))
+  for nd in rec.dws:
+    worst = max(worst, check_dw_node(nd))
+  for nd in rec.bns:
+    worst = max(worst, check_bn_node(nd, sum_terms=True))
+  for kind, si, bi in feeds:
+    if kind == 'dw':
+      check_dw_stats_feed(rec.dws[si], rec.bns[bi])
+    else:
+      check_stats_feed(rec.convs[si], rec.bns[bi])
+  print('mobilenet_v1 chained: %d conv + %d depthwise + %d batch-norm nodes, %d statistics feeds, worst error / bound %.3f'
+        % (len(rec.convs), len(rec.dws), len(rec.bns), len(feeds), worst))
   assert worst <= 1.0

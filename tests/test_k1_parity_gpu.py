@@ -67,6 +67,22 @@ def test_resnet50_layer_shapes_at_batch_128(env):
 
 
 @pytest.mark.skipif(not torch.cuda.is_available(), reason='needs a GPU')
+@pytest.mark.parametrize('env', [
+    {},                                                                          # the built-in selection rules
+    {'RIGL_ROWSTREAM': '2'},                                                     # the row-streaming 1x1 body wherever legal
+    {'RIGL_BWD1X1': '0', 'RIGL_STEM_DIRECT': '0', 'RIGL_WGRAD_IL': '0', 'RIGL_C3X3': '0', 'RIGL_ROWSTREAM': '0', 'RIGL_BWDSLICE': '0'},   # the generic bodies on the layers with kernels of their own
+])
+def test_mobilenet_v1_layer_shapes_at_batch_128(env):
+  """MobileNet-v1 (BASELINE config 5) at the benchmarked per-GPU batch, where kernel selection differs from the small-batch
+  config test: the 3x3 / 2 stem with 3 input channels (the padded-copy path and its ~12.5 k statistics partials), the 9
+  distinct pointwise layers (the row-streaming forward at 56 / 28 / 14, the channel-sliced backward and k_bwdslice64, 32 -> 64
+  over 1.6 M rows, 512 / 1024 -> 1024 at 7x7) and final_dense as a 1024 -> 1000 1x1 conv over 128 rows -- every entry point
+  against the fp64 reference."""
+  out = _run(['--set', 'mobilenet_v1', '--batch', '128'], env, timeout=3000)
+  assert out['cases'] == 11
+
+
+@pytest.mark.skipif(not torch.cuda.is_available(), reason='needs a GPU')
 @pytest.mark.parametrize('env', [{}, {'RIGL_STEM_DIRECT': '0'}])
 def test_imagenet_stem_shapes(env):
   """The 7x7 / 2 stem on the LDS-resident-patch kernels (stem.hpp) and, with the knob off, on the generic bodies over the

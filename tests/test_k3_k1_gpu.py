@@ -1,6 +1,7 @@
 """Parity of K3 (masked SGD-momentum, bit-exact vs the oracle), the weight
 shadow packer, and K1 (MFMA masked conv fwd/dgrad/wgrad vs an fp32 / fp64
 convolution of the same bf16-rounded operands)."""
+import ctypes
 import os
 
 import numpy as np
@@ -10,6 +11,7 @@ torch = pytest.importorskip('torch')
 import torch.nn.functional as F  # noqa: E402
 
 from oracle import rigl_oracle as O  # noqa: E402
+from tests import convref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -436,6 +438,13 @@ def test_depthwise_conv(case):
   assert ((y - ref_y).abs() <= 2.0**-8 * ref_y.abs() + 1e-5 * ref_y.abs().max() + 1e-6).all()
   assert ((dx - ref_dx).abs() <= 2.0**-8 * ref_dx.abs() + 1e-5 * ref_dx.abs().max() + 1e-6).all()
   assert (dw.cpu() - ref_dw).abs().max() <= 1e-4 * ref_dw.abs().max() + 1e-5
+  # ... and per element against the fp64 reference: 2^-8 |ref| + 1e-5 sum|a||b| (y, dx), 1e-5 sum|x||dy| (dw) -- a wrong
+  # scale confined to a few low-energy channels is invisible next to the largest element, not next to its own dot product
+  ref = convref.depthwise_fp64(x, w, dy, stride, pt, pl, Ho, Wo)
+  ab = convref.depthwise_fp64(x.abs(), w.abs(), dy.abs(), stride, pt, pl, Ho, Wo)
+  convref.check_close('y', y, ref['y'], ab['y'], 1e-5, 2.0 ** -8)
+  convref.check_close('dx', dx, ref['dx'], ab['dx'], 1e-5, 2.0 ** -8)
+  convref.check_close('dw', dw.cpu(), ref['dw'].reshape(-1), ab['dw'].reshape(-1), 1e-5)
   # deterministic: the split reduction of the weight gradient has a fixed order
   dw2 = torch.empty_like(dw)
   ops.depthwise_wgrad(d, x.to(DEV), dy.to(DEV), dw2)
@@ -454,6 +463,57 @@ def test_depthwise_conv(case):
     assert torch.equal(part, part2)
   else:
     assert part is None
+
+
+# MobileNet-v1's nine distinct depthwise layers at the benchmarked batch and 224 x 224 (mobilenetv1_model.py:282-298):
+# H = W, C, stride; stride 2 is fixed padding 1 / 1 + VALID, stride 1 is SAME (nn.DepthwiseConv2d)
+MOBILENET_V1_DEPTHWISE = [(112, 32, 1), (112, 64, 2), (56, 128, 1), (56, 128, 2), (28, 256, 1), (28, 256, 2),
+                          (14, 512, 1), (14, 512, 2), (7, 1024, 1)]
+
+
+@pytest.mark.parametrize('layer', MOBILENET_V1_DEPTHWISE)
+def test_mobilenet_v1_depthwise_layers_at_batch_128(layer):
+  """The depthwise kernels at the row counts bench.py runs (the 3x3 strip kernels, up to 12.5 k statistics partials, the
+  weight-gradient part count at its 512 / 8 MB caps) per element against tests/convref.py's fp64 depthwise reference:
+  y, dX within 2^-8 |ref| + 1e-5 sum|a||b|, dW within 1e-5 sum|x||dy|.  The gradient's channels span a 1 : 8 range of
+  magnitudes so that low-energy channels are checked on their own scale.  The forward with statistics leaves y bit for
+  bit and partials whose totals are the fp64 sums of the bf16 outputs; partials and dW repeat bit for bit."""
+  from rigl_amd import _lib, ops
+  HW, C, stride = layer
+  N, k = 128, 3
+  Ho = Wo = (HW - 1) // stride + 1
+  g = torch.Generator(device=DEV).manual_seed(HW * C + stride)
+  x = torch.randn(N, HW, HW, C, generator=g, device=DEV).to(torch.bfloat16)
+  chan = 2.0 ** -(torch.arange(C, device=DEV) % 4).float()                   # exact in bf16
+  dy = (torch.randn(N, Ho, Wo, C, generator=g, device=DEV) * chan).to(torch.bfloat16)
+  w = torch.randn(k, k, C, generator=g, device=DEV) * 0.3
+  wd = w.reshape(-1).contiguous()
+  d = ops.conv_desc(N, HW, HW, C, C, k, k, stride, 1, 1, Ho, Wo)
+  ref = convref.depthwise_fp64(x, w, dy, stride, 1, 1, Ho, Wo)
+  ab = convref.depthwise_fp64(x.abs(), w.abs(), dy.abs(), stride, 1, 1, Ho, Wo)
+  y = ops.depthwise_fwd(d, x, wd)
+  convref.check_close('y', y, ref['y'], ab['y'], 1e-5, 2.0 ** -8)
+  dx = ops.depthwise_dgrad(d, dy, wd)
+  convref.check_close('dx', dx, ref['dx'], ab['dx'], 1e-5, 2.0 ** -8)
+  del dx
+  dw = torch.empty(k * k * C, device=DEV)
+  ops.depthwise_wgrad(d, x, dy, dw)
+  convref.check_close('dw', dw, ref['dw'].reshape(-1), ab['dw'].reshape(-1), 1e-5)
+  del ref, ab
+  dw2 = torch.empty_like(dw)
+  ops.depthwise_wgrad(d, x, dy, dw2)
+  assert torch.equal(dw.view(torch.int32), dw2.view(torch.int32)), 'dw not deterministic'
+  # the statistics forward: what bn_a consumes in every block of the network
+  ys, part = ops.depthwise_fwd(d, x, wd, stats=True)
+  assert torch.equal(ys.view(torch.int16), y.view(torch.int16)), 'the statistics epilogue changed y'
+  assert part is not None and part.shape == (_lib.load().rigl_depthwise_conv2d_stats_parts(ctypes.byref(d)), 2, C)
+  y64 = y.double().reshape(-1, C)
+  tot = part.double().sum(0)
+  convref.check_close('sum y', tot[0], y64.sum(0), y64.abs().sum(0), 1e-5)
+  q = (y64 * y64).sum(0)
+  convref.check_close('sum y^2', tot[1], q, q, 1e-5)
+  _, part2 = ops.depthwise_fwd(d, x, wd, stats=True)
+  assert torch.equal(part.view(torch.int32), part2.view(torch.int32)), 'statistics partials not deterministic'
 
 
 def test_plan_caches_follow_the_knobs_on_a_live_descriptor():
