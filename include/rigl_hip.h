@@ -718,9 +718,48 @@ int rigl_global_avgpool_fwd(int32_t n, int32_t pixels, int32_t c, const rigl_bf1
                             rigl_bf16* y, rigl_stream_t stream);
 int rigl_global_avgpool_bwd(int32_t n, int32_t pixels, int32_t c, const rigl_bf16* dy,
                             rigl_bf16* dx, rigl_stream_t stream);
+/* The spatial mean's gradient through the ReLU in front of it (VGG's last conv):
+ * dx[n,p,c] = bf16(float(dy[n,c]) / P) * [x[n,p,c] > 0], x = the pooled ReLU
+ * output; c % 8 == 0, 16-byte aligned tensors. */
+int rigl_global_avgpool_bwd_relu(int32_t n, int32_t pixels, int32_t c, const rigl_bf16* dy,
+                                 const rigl_bf16* x, rigl_bf16* dx, rigl_stream_t stream);
 int rigl_softmax_xent(int32_t rows, int32_t classes, const rigl_bf16* logits,
                       const int64_t* labels, float label_smoothing, float grad_scale,
                       float* row_loss, rigl_bf16* dlogits /* nullable */, rigl_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Masked conv + ReLU without a batch norm (VGG, rigl/imagenet_resnet/vgg.py:
+ * 124-134: conv2d_fixed_padding followed by tf.nn.relu).
+ *   rigl_masked_conv2d_fwd_relu: y = bf16(max(conv(x, w), 0)), +0 for every
+ *     non-positive value, applied after the complete reduction; the
+ *     pre-activation is never stored.
+ *   rigl_masked_conv2d_bwd_relu: dW (dense fp32) as rigl_masked_conv2d_bwd and
+ *     dX = bf16(dgrad(dy)) * [x > 0].  x is the conv's input AND a ReLU output
+ *     (or a max pool of one: at the pool winner the ReLU output is the pooled
+ *     value), so dX is the gradient the ReLU in front passes on; dy must arrive
+ *     gated by this conv's own ReLU (its consumer's dX, or
+ *     rigl_global_avgpool_bwd_relu).
+ * Both run the ReLU in the epilogue of the body the layer selects where that
+ * body has one (rigl_conv2d_fwd_takes_relu_epilogue /
+ * rigl_conv2d_bwd_takes_relu_epilogue = 1: the igemm and ping-pong bodies),
+ * else the plain kernels followed by the stand-alone passes below; the bits
+ * are the same either way.  Knob "relu_fuse" = 0 forces the stand-alone passes.
+ *   rigl_relu_fwd: y = relu(x) (in place allowed); rigl_relu_bwd: dx = dy *
+ *   [x > 0] (in place on dy allowed).  n % 8 == 0, 16-byte aligned tensors.
+ * Shapes whose bf16 tensors reach 2^30 elements: RIGL_EUNSUPPORTED.
+ * ---------------------------------------------------------------------- */
+int32_t rigl_conv2d_fwd_takes_relu_epilogue(const RiglConvDesc* d);
+int32_t rigl_conv2d_bwd_takes_relu_epilogue(const RiglConvDesc* d);
+int rigl_masked_conv2d_fwd_relu(const RiglConvDesc* d, const rigl_bf16* x,
+                                const rigl_bf16* w_ohwi, rigl_bf16* y, void* workspace,
+                                size_t workspace_bytes, rigl_stream_t stream);
+int rigl_masked_conv2d_bwd_relu(const RiglConvDesc* d, const rigl_bf16* x,
+                                const rigl_bf16* dy, const rigl_bf16* w_hwio, float* dw,
+                                rigl_bf16* dx, void* workspace, size_t workspace_bytes,
+                                rigl_stream_t stream);
+int rigl_relu_fwd(int64_t n, const rigl_bf16* x, rigl_bf16* y, rigl_stream_t stream);
+int rigl_relu_bwd(int64_t n, const rigl_bf16* dy, const rigl_bf16* x, rigl_bf16* dx,
+                  rigl_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Evaluation (the reference's EVAL mode, imagenet_train_eval.py:596-615 and

@@ -175,6 +175,13 @@ SIGNATURES = {
     'rigl_global_avgpool_fwd': (C.c_int, [_I32, _I32, _I32, _P, _P, _P]),
     'rigl_global_avgpool_bwd': (C.c_int, [_I32, _I32, _I32, _P, _P, _P]),
     'rigl_softmax_xent': (C.c_int, [_I32, _I32, _P, _P, _F, _F, _P, _P, _P]),
+    'rigl_global_avgpool_bwd_relu': (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P]),
+    'rigl_conv2d_fwd_takes_relu_epilogue': (C.c_int32, [C.POINTER(ConvDesc)]),
+    'rigl_conv2d_bwd_takes_relu_epilogue': (C.c_int32, [C.POINTER(ConvDesc)]),
+    'rigl_masked_conv2d_fwd_relu': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _SZ, _P]),
+    'rigl_masked_conv2d_bwd_relu': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    'rigl_relu_fwd': (C.c_int, [_I64, _P, _P, _P]),
+    'rigl_relu_bwd': (C.c_int, [_I64, _P, _P, _P, _P]),
     'rigl_bn_infer_params_batched': (C.c_int, [C.POINTER(BnInferItem), _I32, _P]),
     'rigl_bn_apply': (C.c_int, [_I64, _I32, _P, _P, _P, _I32, _P, _P]),
     'rigl_bn_apply_pair': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _I32, _P, _P]),

@@ -85,4 +85,22 @@ inline void prof_launch(F kernel, dim3 grid, dim3 blk, unsigned lds, hipStream_t
 inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// ---- ReLU on packed bf16 pairs (the VGG convs: no batch norm between conv and ReLU) ----------------------------
+// relu: every value with the sign bit set (negatives and -0) becomes +0; max(bf16(acc), 0) == bf16(max(acc, 0)).
+__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {
+  return v & ~(((v & 0x80008000u) >> 15) * 0xFFFFu);
+}
+// gate: v where x > 0 (sign clear and not zero), else +0 -- the ReLU derivative read off the ReLU's own output.
+__device__ __forceinline__ uint32_t gate_bf16x2(uint32_t v, uint32_t x) {
+  const uint32_t lo = (x & 0xFFFFu) - 1u < 0x7FFFu ? 0x0000FFFFu : 0u;
+  const uint32_t hi = (x >> 16) - 1u < 0x7FFFu ? 0xFFFF0000u : 0u;
+  return v & (lo | hi);
+}
+__device__ __forceinline__ uint4 relu_bf16x8(uint4 v) {
+  return make_uint4(relu_bf16x2(v.x), relu_bf16x2(v.y), relu_bf16x2(v.z), relu_bf16x2(v.w));
+}
+__device__ __forceinline__ uint4 gate_bf16x8(uint4 v, uint4 x) {
+  return make_uint4(gate_bf16x2(v.x, x.x), gate_bf16x2(v.y, x.y), gate_bf16x2(v.z, x.z), gate_bf16x2(v.w, x.w));
+}
+
 }  // namespace rigl

@@ -172,7 +172,8 @@ struct IgemmArgs {
   const uint16_t* A;   // gathered activation tensor (x for fwd, dy for dgrad), NHWC
   const uint16_t* B;   // packed weights
   void* C;             // output rows
-  const uint16_t* ADD; // optional bf16 tensor added to the bf16 output rows (same layout as C), or NULL
+  const uint16_t* ADD; // optional bf16 tensor added to the bf16 output rows (same layout as C), or NULL.  A dgrad with the
+                       // ReLU epilogue (EPI_RELU) reads it as the conv's INPUT x instead: out = bf16(acc) * [x > 0]
   // ADD of a SUBSAMPLED view (add_sh > 0): the addend has one row per output pixel (hi, wi) with hi % add_sh == 0 and
   // wi % add_sw == 0, laid out [image][add_ho][add_wo][N]; every other pixel adds nothing.  (The gradient of a strided
   // 1x1 conv that read the same tensor: rigl_masked_conv2d_bwd_sub.)
@@ -238,7 +239,12 @@ constexpr int igemm_smem_bytes() {
   return BASE;
 }
 
-template <int TM, int TN, int BK, int MODE /*0 fwd, 1 dgrad*/, bool OUT_F32, bool CLS, int STAGES, int WM = 2>
+// Epilogue variants of the bf16 bodies (a template parameter: the EPI_NONE instantiations are the kernels as they were).
+// EPI_RELU: forward y = bf16(max(acc, 0)) (+0 for every non-positive value); dgrad dX = bf16(acc) * [x > 0] with x = the conv's
+// input in P.ADD -- the gradient a ReLU (or a max pool of one) in front of this conv passes on (the VGG convs, vgg.py:124-134).
+enum { EPI_NONE = 0, EPI_RELU = 1 };
+
+template <int TM, int TN, int BK, int MODE /*0 fwd, 1 dgrad*/, bool OUT_F32, bool CLS, int STAGES, int WM = 2, int EPIK = EPI_NONE>
 __device__ __forceinline__ void igemm_body(const IgemmArgs& P, unsigned char* smem, uint32_t bid, uint32_t nblk) {
   constexpr int NST = STAGES;
   constexpr int THREADS = 128 * WM;        // (shadows the file-wide 256 inside this body)
@@ -670,10 +676,13 @@ __device__ __forceinline__ void igemm_body(const IgemmArgs& P, unsigned char* sm
         const int m = CLS ? rowpix[row] : m0 + row, n = n0 + ch * 8;
         if (m >= 0 && m < P.M && n < P.N) {
           uint4 v = *reinterpret_cast<const uint4*>(Cs + row * CS_LD + ch * 8);
-          if (P.ADD) {   // fused gradient accumulation: out = bf16(bf16(acc) + addend), as the separate add would give
+          if (EPIK == EPI_RELU && MODE == 1) {
+            v = gate_bf16x8(v, addv[it]);      // (the x tile: loaded above as the addend is)
+          } else if (P.ADD) {   // fused gradient accumulation: out = bf16(bf16(acc) + addend), as the separate add would give
             const uint4 q = addv[it];
             v.x = add_bf16x2(v.x, q.x); v.y = add_bf16x2(v.y, q.y); v.z = add_bf16x2(v.z, q.z); v.w = add_bf16x2(v.w, q.w);
           }
+          if (EPIK == EPI_RELU && MODE == 0) v = relu_bf16x8(v);
           store16(C + (int64_t)m * P.ldc + n, v);
         }
       }
@@ -777,6 +786,17 @@ template <int MODE, bool CLS>
 __global__ __launch_bounds__(512) void k_igemm_big(IgemmArgs P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_big[];
   igemm_body<2, 2, 32, MODE, false, CLS, 3, 4>(P, smem_big, blockIdx.x, gridDim.x);
+}
+// The same two kernels with the ReLU epilogue (bf16 output only)
+template <int TM, int TN, int BK, int MODE, bool CLS, int STAGES>
+__global__ __launch_bounds__(THREADS) void k_igemm_relu(IgemmArgs P) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[igemm_smem_bytes<TM, TN, BK, MODE, false, CLS, STAGES>()];
+  igemm_body<TM, TN, BK, MODE, false, CLS, STAGES, 2, EPI_RELU>(P, smem, blockIdx.x, gridDim.x);
+}
+template <int MODE>
+__global__ __launch_bounds__(512) void k_igemm_big_relu(IgemmArgs P) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_big[];
+  igemm_body<2, 2, 32, MODE, false, false, 3, 4, EPI_RELU>(P, smem_big, blockIdx.x, gridDim.x);
 }
 // ------------------------------------------------------------------ wgrad
 struct WgradArgs {
@@ -1109,6 +1129,14 @@ __global__ __launch_bounds__(THREADS) void k_bwd_fused(IgemmArgs PD, WgradArgs P
   if (blockIdx.x < nw) wgrad_tr_body<TMW, TNW, STW>(PW, smem, blockIdx.x, nw);
   else igemm_body<2, TND, 32, 1, false, CLSD, 3>(PD, smem, blockIdx.x - nw, nd);
 }
+// ... with the ReLU-gated dgrad (EPI_RELU: PD.ADD = the conv's input)
+template <int TND, bool CLSD, int TMW, int TNW, int STW>
+__global__ __launch_bounds__(THREADS) void k_bwd_fused_relu(IgemmArgs PD, WgradArgs PW, uint32_t nd, uint32_t nw) {
+  constexpr int SD = igemm_smem_bytes<2, TND, 32, 1, false, CLSD, 3>(), SW = wgrad_tr_smem_bytes<TMW, TNW, STW>();
+  __shared__ __attribute__((aligned(16))) unsigned char smem[SD > SW ? SD : SW];
+  if (blockIdx.x < nw) wgrad_tr_body<TMW, TNW, STW>(PW, smem, blockIdx.x, nw);
+  else igemm_body<2, TND, 32, 1, false, CLSD, 3, 2, EPI_RELU>(PD, smem, blockIdx.x - nw, nd);
+}
 
 // ------------------------------------------------------------------ small-Cin (stem) path
 // Explicit im2col for layers whose Cin is not a multiple of 8 (the 7x7x3 stem):
@@ -1238,9 +1266,20 @@ __global__ __launch_bounds__(THREADS) void k_mfma_probe(float* __restrict__ sink
 }
 
 // ------------------------------------------------------------------ dispatch
-template <int MODE, bool F32, bool CLS>
+template <int MODE, bool F32, bool CLS, int EPI = EPI_NONE>
 static void launch_igemm_t(const IgemmArgs& a, dim3 grid, bool wide_n, bool dma, hipStream_t st) {
   dim3 blk(THREADS);
+  if constexpr (EPI != EPI_NONE) {
+    static_assert(!F32, "the ReLU epilogue is a bf16 epilogue");
+    if (dma) {
+      if (wide_n) RIGL_K_LAUNCH((k_igemm_relu<2, 2, 32, MODE, CLS, 3>), grid, blk, 0, st, a);
+      else RIGL_K_LAUNCH((k_igemm_relu<2, 1, 32, MODE, CLS, 3>), grid, blk, 0, st, a);
+    } else {
+      if (wide_n) RIGL_K_LAUNCH((k_igemm_relu<2, 2, 16, MODE, CLS, 2>), grid, blk, 0, st, a);
+      else RIGL_K_LAUNCH((k_igemm_relu<2, 1, 16, MODE, CLS, 2>), grid, blk, 0, st, a);
+    }
+    return;
+  }
   if (dma) {   // LDS-DMA ring, BK = 32: 3 stages = 48 KB of LDS -> 3 workgroups per CU (the 136-VGPR limit too)
     if (wide_n) RIGL_K_LAUNCH((k_igemm<2, 2, 32, MODE, F32, CLS, 3>), grid, blk, 0, st, a);
     else RIGL_K_LAUNCH((k_igemm<2, 1, 32, MODE, F32, CLS, 3>), grid, blk, 0, st, a);
@@ -1317,16 +1356,36 @@ static IgemmPlan plan_igemm(IgemmArgs& a) {
   return pl;
 }
 
-template <int MODE, bool F32>
+template <int MODE>
+static bool big_relu_ready() {
+  static const bool ready = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_igemm_big_relu<MODE>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                igemm_smem_bytes<2, 2, 32, MODE, false, false, 3, 4>()) == hipSuccess;
+  return ready;
+}
+
+template <int MODE, bool F32, int EPI = EPI_NONE>
 static void launch_igemm(const IgemmArgs& a0, hipStream_t st) {
   IgemmArgs a = a0;
   const IgemmPlan pl = plan_igemm<MODE>(a);
   if (!F32 && pl.big) {
-    RIGL_K_LAUNCH((k_igemm_big<MODE, false>), dim3(pl.grid), dim3(512), (igemm_smem_bytes<2, 2, 32, MODE, false, false, 3, 4>()), st, a);
+    if constexpr (EPI != EPI_NONE) {
+      if (big_relu_ready<MODE>()) {
+        RIGL_K_LAUNCH((k_igemm_big_relu<MODE>), dim3(pl.grid), dim3(512), (igemm_smem_bytes<2, 2, 32, MODE, false, false, 3, 4>()), st, a);
+        return;
+      }
+    } else {
+      RIGL_K_LAUNCH((k_igemm_big<MODE, false>), dim3(pl.grid), dim3(512), (igemm_smem_bytes<2, 2, 32, MODE, false, false, 3, 4>()), st, a);
+      return;
+    }
+  }
+  if (EPI != EPI_NONE && pl.big) {   // (only the ReLU twin of the big kernel refused its LDS: 128-row tiles instead)
+    a.tiles_n = (a.N + 127) / 128;
+    launch_igemm_t<MODE, F32, false, EPI>(a, dim3((unsigned)((a.M + 127) / 128 * a.tiles_n)), true, true, st);
     return;
   }
-  if (pl.cls) launch_igemm_t<MODE, F32, true>(a, dim3(pl.grid), pl.wide_n, pl.dma, st);
-  else launch_igemm_t<MODE, F32, false>(a, dim3(pl.grid), pl.wide_n, pl.dma, st);
+  if (pl.cls) launch_igemm_t<MODE, F32, true, EPI>(a, dim3(pl.grid), pl.wide_n, pl.dma, st);
+  else launch_igemm_t<MODE, F32, false, EPI>(a, dim3(pl.grid), pl.wide_n, pl.dma, st);
 }
 
 static int check_desc(const RiglConvDesc* d, const char* who) {
@@ -1475,9 +1534,65 @@ int32_t rigl_conv2d_stats_parts(const RiglConvDesc* d) {
   return (int32_t)((M + 127) / 128);     // one partial per 128-row output tile
 }
 
+}  // extern "C"
+
+namespace rigl {
+int relu_fwd_launch(int64_t n, const rigl_bf16* x, rigl_bf16* y, hipStream_t st);                          // relu.hip
+int relu_bwd_launch(int64_t n, const rigl_bf16* dy, const rigl_bf16* x, rigl_bf16* dx, hipStream_t st);
+namespace k1 {
+// Does the forward body this layer selects carry the ReLU epilogue (EPI_RELU)?  The igemm and ping-pong bodies do (the
+// padded tiny-Cin input path included); the row-streaming, c3x3 and direct-stem bodies do not.  Knob "relu_fuse" = 0: no
+// layer (the stand-alone passes everywhere: the A/B switch).
+static bool relu_fwd_fusable(const RiglConvDesc* d) {
+  if (RIGL_TUNE("relu_fuse", 1) == 0 || (d->cout % 8)) return false;
+  if (tiny_cin(d)) return !stem_direct_legal(d);
+  if (small_cin(d)) return true;
+  return !rs_use<0>(d) && !c3x3_use(d);
+}
+// ... and the dgrad body of its one-call backward (the shared igemm / ping-pong launches, or the stand-alone igemm /
+// ping-pong dgrad behind a separate weight gradient)
+static bool relu_dgrad_fusable(const RiglConvDesc* d) {
+  if (RIGL_TUNE("relu_fuse", 1) == 0 || (d->cin % 8) || (d->cout % 8)) return false;
+  return !bwd1x1_kind(d) && !bs_use(d) && !rs_use<1>(d) && !c3x3_use(d);
+}
+}  // namespace k1
+}  // namespace rigl
+
+static int fwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* w_ohwi, rigl_bf16* y, float* stats,
+                    size_t stats_floats, void* workspace, size_t workspace_bytes, rigl_stream_t stream, int epi);
+
+extern "C" {
+
 int rigl_masked_conv2d_fwd_stats(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* w_ohwi, rigl_bf16* y,
                                  float* stats, size_t stats_floats, void* workspace, size_t workspace_bytes,
                                  rigl_stream_t stream) {
+  return fwd_impl(d, x, w_ohwi, y, stats, stats_floats, workspace, workspace_bytes, stream, rigl::k1::EPI_NONE);
+}
+
+int32_t rigl_conv2d_fwd_takes_relu_epilogue(const RiglConvDesc* d) {
+  using namespace rigl;
+  using namespace rigl::k1;
+  if (!d || check_desc(d, "rigl_conv2d_fwd_takes_relu_epilogue")) return 0;
+  return relu_fwd_fusable(d) ? 1 : 0;
+}
+
+int rigl_masked_conv2d_fwd_relu(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* w_ohwi, rigl_bf16* y,
+                                void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
+  using namespace rigl;
+  using namespace rigl::k1;
+  int rc = check_desc(d, "rigl_masked_conv2d_fwd_relu");
+  if (rc) return rc;
+  if (d->cout % 8) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_fwd_relu: cout %% 8 != 0");
+  if (relu_fwd_fusable(d)) return fwd_impl(d, x, w_ohwi, y, nullptr, 0, workspace, workspace_bytes, stream, EPI_RELU);
+  rc = fwd_impl(d, x, w_ohwi, y, nullptr, 0, workspace, workspace_bytes, stream, EPI_NONE);
+  if (rc) return rc;
+  return relu_fwd_launch((int64_t)d->n * d->ho * d->wo * d->cout, y, y, as_stream(stream));
+}
+
+}  // extern "C"
+
+static int fwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* w_ohwi, rigl_bf16* y, float* stats,
+                    size_t stats_floats, void* workspace, size_t workspace_bytes, rigl_stream_t stream, int epi) {
   using namespace rigl;
   using namespace rigl::k1;
   int rc = check_desc(d, "rigl_masked_conv2d_fwd");
@@ -1553,15 +1668,18 @@ int rigl_masked_conv2d_fwd_stats(const RiglConvDesc* d, const rigl_bf16* x, cons
       a.KS_CNT = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + (size_t)pp.grid * 2 * pp.bm * pp.bn * 4);
       RIGL_HIP(hipMemsetAsync(a.KS_CNT, 0, (size_t)pp.grid * 4, st));
     }
-    if (pp.variant && launch_pp<0>(pp, a, st)) {
+    if (pp.variant && (epi == EPI_RELU ? launch_pp<0, EPI_RELU>(pp, a, st) : launch_pp<0>(pp, a, st))) {
       RIGL_CHECK_LAUNCH("rigl_masked_conv2d_fwd");
       return RIGL_OK;
     }
   }
-  launch_igemm<0, false>(a, st);
+  if (epi == EPI_RELU) launch_igemm<0, false, EPI_RELU>(a, st);
+  else launch_igemm<0, false>(a, st);
   RIGL_CHECK_LAUNCH("rigl_masked_conv2d_fwd");
   return RIGL_OK;
 }
+
+extern "C" {
 
 // y = conv(relu(bn(x_pre)), w) with the apply pass of the batch norm done on the operand load (rowstream.hpp, BNL kernels):
 // scale_shift = [2][cin] fp32 (rows 2-3 of the batch norm's `saved`), a_out = the activated tensor, written as a side output.
@@ -1682,8 +1800,11 @@ static void set_addend_sub(rigl::k1::IgemmArgs& a, const RiglConvDesc* d, Addend
   a.add_ho = (d->h + s.sh - 1) / s.sh; a.add_wo = (d->w + s.sw - 1) / s.sw;
 }
 
+// epi = EPI_RELU (rigl_masked_conv2d_bwd_relu, only where relu_dgrad_fusable): `addend` is the conv's input x, whose sign
+// gates dX in the igemm / ping-pong dgrad epilogue
 static int dgrad_impl(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio, const rigl_bf16* addend,
-                      rigl_bf16* dx, const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub = {1, 1});
+                      rigl_bf16* dx, const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub = {1, 1},
+                      int epi = rigl::k1::EPI_NONE);
 
 int rigl_masked_conv2d_dgrad_acc(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio,
                                  const rigl_bf16* addend, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
@@ -1693,7 +1814,7 @@ int rigl_masked_conv2d_dgrad_acc(const RiglConvDesc* d, const rigl_bf16* dy, con
 }
 
 static int dgrad_impl(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio, const rigl_bf16* addend,
-                      rigl_bf16* dx, const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub) {
+                      rigl_bf16* dx, const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub, int epi) {
   using namespace rigl;
   using namespace rigl::k1;
   int rc = check_desc(d, "rigl_masked_conv2d_dgrad");
@@ -1745,11 +1866,12 @@ static int dgrad_impl(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf1
   rc = attach_bn(a, d, bn);
   if (rc) return rc;
   const PPPlan pp = plan_pp<1>(a);
-  if (pp.variant && launch_pp<1>(pp, a, st)) {
+  if (pp.variant && (epi == EPI_RELU ? launch_pp<1, EPI_RELU>(pp, a, st) : launch_pp<1>(pp, a, st))) {
     RIGL_CHECK_LAUNCH("rigl_masked_conv2d_dgrad");
     return RIGL_OK;
   }
-  launch_igemm<1, false>(a, st);
+  if (epi == EPI_RELU) launch_igemm<1, false, EPI_RELU>(a, st);
+  else launch_igemm<1, false>(a, st);
   RIGL_CHECK_LAUNCH("rigl_masked_conv2d_dgrad");
   return RIGL_OK;
 }
@@ -1865,7 +1987,7 @@ int rigl_masked_conv2d_wgrad(const RiglConvDesc* d, const rigl_bf16* x, const ri
 static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
                     const rigl_bf16* addend, float* dw, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
                     const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub = {1, 1},
-                    const RiglConvDesc* dg = nullptr, const uint8_t* addend_bits = nullptr);
+                    const RiglConvDesc* dg = nullptr, const uint8_t* addend_bits = nullptr, int epi = rigl::k1::EPI_NONE);
 
 // rigl_masked_conv2d_bwd with the batch-norm backward reductions of the tensor dX is the gradient of riding in the dgrad
 // epilogue.
@@ -1879,7 +2001,7 @@ int rigl_masked_conv2d_bwd_bn(const RiglConvDesc* d, const rigl_bf16* x, const r
 static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
                     const rigl_bf16* addend, float* dw, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
                     const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub, const RiglConvDesc* dg,
-                    const uint8_t* addend_bits) {
+                    const uint8_t* addend_bits, int epi) {
   // dg (rigl_masked_conv2d_bwd_grid): the dgrad half runs on THIS descriptor -- the stride-1 twin of a strided 1x1 conv
   // on its own output grid -- while the weight gradient reads x through d; the two halves of the shared launch take
   // their geometry from separate argument blocks anyway.
@@ -1982,7 +2104,7 @@ static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* 
       const WgradArgs aw = pp_wgrad_args(d, x, dy, pw, dw, workspace);
       ad.fd_rw = make_fastdiv(ad.RW); ad.fd_rh = make_fastdiv(ad.RH);
       ad.tiles_n = ad.N / bn2;
-      if (pp_bwd_launch(dvar, strided, ad, aw, pw, st)) {
+      if (epi == EPI_RELU ? pp_bwd_launch<EPI_RELU>(dvar, strided, ad, aw, pw, st) : pp_bwd_launch(dvar, strided, ad, aw, pw, st)) {
         if (pw.splits > 1) {
           ReduceArgs ra = {static_cast<const float*>(workspace), dw, pw.slab, pw.slab, pw.splits};
           launch_wgrad_reduce(ra, st);
@@ -2017,15 +2139,20 @@ static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* 
       aw.OUT = two_pass ? static_cast<float*>(workspace) : dw;
       const unsigned nd = pd.grid, nw = (unsigned)((int64_t)p.tiles_ci * p.tiles_co * aw.KH * aw.KW * p.splits);
       const dim3 grid(nd + nw), blk(THREADS);
-#define RIGL_FUSED(TND, CLSD)                                                                                          \
+#define RIGL_FUSED(KB, TND, CLSD)                                                                                      \
       {                                                                                                                \
-        if (p.tm == 2 && p.tn == 2) RIGL_K_LAUNCH((k_bwd_fused<TND, CLSD, 2, 2, 3>), grid, blk, 0, st, ad, aw, nd, nw); \
-        else if (p.tm == 2) RIGL_K_LAUNCH((k_bwd_fused<TND, CLSD, 2, 1, 4>), grid, blk, 0, st, ad, aw, nd, nw);          \
-        else if (p.tn == 2) RIGL_K_LAUNCH((k_bwd_fused<TND, CLSD, 1, 2, 4>), grid, blk, 0, st, ad, aw, nd, nw);          \
-        else RIGL_K_LAUNCH((k_bwd_fused<TND, CLSD, 1, 1, 4>), grid, blk, 0, st, ad, aw, nd, nw);                         \
+        if (p.tm == 2 && p.tn == 2) RIGL_K_LAUNCH((KB<TND, CLSD, 2, 2, 3>), grid, blk, 0, st, ad, aw, nd, nw);          \
+        else if (p.tm == 2) RIGL_K_LAUNCH((KB<TND, CLSD, 2, 1, 4>), grid, blk, 0, st, ad, aw, nd, nw);                   \
+        else if (p.tn == 2) RIGL_K_LAUNCH((KB<TND, CLSD, 1, 2, 4>), grid, blk, 0, st, ad, aw, nd, nw);                   \
+        else RIGL_K_LAUNCH((KB<TND, CLSD, 1, 1, 4>), grid, blk, 0, st, ad, aw, nd, nw);                                  \
       }
-      if (pd.wide_n) { if (pd.cls) RIGL_FUSED(2, true) else RIGL_FUSED(2, false) }
-      else { if (pd.cls) RIGL_FUSED(1, true) else RIGL_FUSED(1, false) }
+      if (epi == EPI_RELU) {
+        if (pd.wide_n) { if (pd.cls) RIGL_FUSED(k_bwd_fused_relu, 2, true) else RIGL_FUSED(k_bwd_fused_relu, 2, false) }
+        else { if (pd.cls) RIGL_FUSED(k_bwd_fused_relu, 1, true) else RIGL_FUSED(k_bwd_fused_relu, 1, false) }
+      } else {
+        if (pd.wide_n) { if (pd.cls) RIGL_FUSED(k_bwd_fused, 2, true) else RIGL_FUSED(k_bwd_fused, 2, false) }
+        else { if (pd.cls) RIGL_FUSED(k_bwd_fused, 1, true) else RIGL_FUSED(k_bwd_fused, 1, false) }
+      }
 #undef RIGL_FUSED
       if (two_pass) {
         const int64_t n_out = (int64_t)d->kh * d->kw * d->cin * d->cout;
@@ -2038,7 +2165,33 @@ static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* 
   }
   rc = rigl_masked_conv2d_wgrad(d, x, dy, dw, workspace, workspace_bytes, stream);
   if (rc || !dx) return rc;
-  return dgrad_impl(dd, dy, w_hwio, addend, dx, bn, stream, sub);
+  return dgrad_impl(dd, dy, w_hwio, addend, dx, bn, stream, sub, epi);
+}
+
+// Backward of y = relu(conv(x, w)) where x is itself the output of a ReLU (or a max pool of one) and dy arrives already
+// gated by [y > 0] (its consumer did that): dW as rigl_masked_conv2d_bwd, dX = bf16(dgrad(dy)) * [x > 0] -- the gradient
+// the ReLU in front of this conv passes on.  Fused into the dgrad epilogue where the layer's body takes it
+// (rigl_conv2d_bwd_takes_relu_epilogue), else the plain backward and the stand-alone rigl_relu_bwd on dX: the same bits.
+int32_t rigl_conv2d_bwd_takes_relu_epilogue(const RiglConvDesc* d) {
+  using namespace rigl;
+  using namespace rigl::k1;
+  if (!d || check_desc(d, "rigl_conv2d_bwd_takes_relu_epilogue")) return 0;
+  return relu_dgrad_fusable(d) ? 1 : 0;
+}
+
+int rigl_masked_conv2d_bwd_relu(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
+                                float* dw, rigl_bf16* dx, void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
+  using namespace rigl;
+  using namespace rigl::k1;
+  int rc = check_desc(d, "rigl_masked_conv2d_bwd_relu");
+  if (rc) return rc;
+  if (!x || !dy || !w_hwio || !dw || !dx) return fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd_relu: NULL tensor");
+  if ((d->cin % 8) || (d->cout % 8)) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_relu: cin/cout %% 8 != 0");
+  if (relu_dgrad_fusable(d))
+    return bwd_impl(d, x, dy, w_hwio, x, dw, dx, workspace, workspace_bytes, nullptr, stream, AddendSub{1, 1}, nullptr, nullptr, EPI_RELU);
+  rc = bwd_impl(d, x, dy, w_hwio, nullptr, dw, dx, workspace, workspace_bytes, nullptr, stream);
+  if (rc) return rc;
+  return relu_bwd_launch((int64_t)d->n * d->h * d->w * d->cin, dx, x, dx, as_stream(stream));
 }
 
 // Whole backward of one masked conv in one call: dW (dense) and, when dx is given, dX (+ addend).

@@ -69,7 +69,9 @@ struct PPCursor { int tap, cb, r, s; };
 // a tile never mixes classes, so it only visits the filter taps that can reach its pixels (3x3 / 2: 4, 2, 2 or 1 taps;
 // 1x1 / 2: three classes have none and just write zeros), and inside a class the gathered dY pixel moves by -1 per
 // visited tap, like a stride-1 dgrad.
-template <int WM, int WN, int TM, int TN, int PH, int MODE /*0 fwd, 1 dgrad*/, bool CLS = false>
+// EPI (conv.hip, EPI_NONE / EPI_RELU): the ReLU epilogues of igemm_body -- forward y = bf16(max(acc, 0)), dgrad dX =
+// bf16(acc) * [x > 0] with the conv's input x in P.ADD.
+template <int WM, int WN, int TM, int TN, int PH, int MODE /*0 fwd, 1 dgrad*/, bool CLS = false, int EPI = EPI_NONE>
 __device__ __forceinline__ void pp_igemm_body(const IgemmArgs& P, unsigned char* const smem, uint32_t bid, uint32_t nblk) {
   static_assert(!CLS || MODE == 1, "parity classes are a dgrad notion");
   using G = PPGeom<WM, WN, TM, TN, PH>;
@@ -367,10 +369,13 @@ __device__ __forceinline__ void pp_igemm_body(const IgemmArgs& P, unsigned char*
         }
       }
       if (m >= 0) {
-        if (P.ADD) {
+        if (EPI == EPI_RELU && MODE == 1) {
+          v = gate_bf16x8(v, addv[it]);
+        } else if (P.ADD) {
           const uint4 q = addv[it];
           v.x = add_bf16x2(v.x, q.x); v.y = add_bf16x2(v.y, q.y); v.z = add_bf16x2(v.z, q.z); v.w = add_bf16x2(v.w, q.w);
         }
+        if (EPI == EPI_RELU && MODE == 0) v = relu_bf16x8(v);
         store16(C + (int64_t)m * P.ldc + ncol, v);
       }
     }
@@ -409,6 +414,11 @@ template <int WM, int WN, int TM, int TN, int PH, int MODE, bool CLS = false>
 __global__ __launch_bounds__(512) void k_igemm_pp(IgemmArgs P) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem_pp[];
   pp_igemm_body<WM, WN, TM, TN, PH, MODE, CLS>(P, smem_pp, blockIdx.x, gridDim.x);
+}
+template <int WM, int WN, int TM, int TN, int PH, int MODE, bool CLS = false>
+__global__ __launch_bounds__(512) void k_igemm_pp_relu(IgemmArgs P) {
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem_pp[];
+  pp_igemm_body<WM, WN, TM, TN, PH, MODE, CLS, EPI_RELU>(P, smem_pp, blockIdx.x, gridDim.x);
 }
 
 // ---- weight gradient on the same skeleton ---------------------------------------------------------------------------------
@@ -593,6 +603,18 @@ __global__ __launch_bounds__(512) void k_bwd_pp(IgemmArgs PD, WgradArgs PW, uint
     pp_igemm_body<WMD, WND, TMD, TND, PHD, 1, CLSD>(PD, smem_pp, wgrad_first ? b - nw : b, nd);
   }
 }
+// ... with the ReLU-gated dgrad (PD.ADD = the conv's input)
+template <int WMD, int WND, int TMD, int TND, int PHD, bool CLSD = false>
+__global__ __launch_bounds__(512) void k_bwd_pp_relu(IgemmArgs PD, WgradArgs PW, uint32_t nd, uint32_t nw, uint32_t wgrad_first) {
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem_pp[];
+  const uint32_t b = blockIdx.x;
+  const bool is_w = wgrad_first ? b < nw : b >= nd;
+  if (is_w) {
+    pp_wgrad_body<2>(PW, smem_pp, wgrad_first ? b : b - nd, nw);
+  } else {
+    pp_igemm_body<WMD, WND, TMD, TND, PHD, 1, CLSD, EPI_RELU>(PD, smem_pp, wgrad_first ? b - nw : b, nd);
+  }
+}
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // Variant ids (rigl_tune_set("pp_fwd" / "pp_dgrad", id) forces one; 0 = never; -1 = the built-in rule)
@@ -602,17 +624,21 @@ struct PPPlan { int variant; unsigned grid; int bm, bn; };
 
 
 
-template <int WM, int WN, int TM, int TN, int PH, int MODE, bool CLS = false>
+template <int WM, int WN, int TM, int TN, int PH, int MODE, bool CLS = false, int EPI = EPI_NONE>
 static bool pp_ready() {
-  static const bool ready = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_igemm_pp<WM, WN, TM, TN, PH, MODE, CLS>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,
+  const void* k = EPI == EPI_RELU ? reinterpret_cast<const void*>(&k_igemm_pp_relu<WM, WN, TM, TN, PH, MODE, CLS>)
+                                  : reinterpret_cast<const void*>(&k_igemm_pp<WM, WN, TM, TN, PH, MODE, CLS>);
+  static const bool ready = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                 PPGeom<WM, WN, TM, TN, PH>::SMEM) == hipSuccess;
   return ready;
 }
-template <int WM, int WN, int TM, int TN, int PH, int MODE, bool CLS = false>
+template <int WM, int WN, int TM, int TN, int PH, int MODE, bool CLS = false, int EPI = EPI_NONE>
 static bool pp_launch_one(dim3 grid, const IgemmArgs& a, hipStream_t st) {
-  if (!pp_ready<WM, WN, TM, TN, PH, MODE, CLS>()) return false;
-  RIGL_K_LAUNCH((k_igemm_pp<WM, WN, TM, TN, PH, MODE, CLS>), grid, dim3(512), (PPGeom<WM, WN, TM, TN, PH>::SMEM), st, a);
+  if (!pp_ready<WM, WN, TM, TN, PH, MODE, CLS, EPI>()) return false;
+  if constexpr (EPI == EPI_RELU)
+    RIGL_K_LAUNCH((k_igemm_pp_relu<WM, WN, TM, TN, PH, MODE, CLS>), grid, dim3(512), (PPGeom<WM, WN, TM, TN, PH>::SMEM), st, a);
+  else
+    RIGL_K_LAUNCH((k_igemm_pp<WM, WN, TM, TN, PH, MODE, CLS>), grid, dim3(512), (PPGeom<WM, WN, TM, TN, PH>::SMEM), st, a);
   return true;
 }
 // Parity-class tables of a strided dgrad on tiles of bm rows (the igemm plan's, on this body's tile height); returns
@@ -734,7 +760,7 @@ static inline bool pp_ksplit_ok(const IgemmArgs& a, const PPPlan& p) {
   return 2 * (int64_t)p.grid <= (int64_t)num_cus() && kt >= min_kt;
 }
 
-template <int MODE>
+template <int MODE, int EPI = EPI_NONE>
 static bool launch_pp(const PPPlan& p, const IgemmArgs& a0, hipStream_t st) {
   IgemmArgs a = a0;
   a.fd_rw = make_fastdiv(a.RW); a.fd_rh = make_fastdiv(a.RH);
@@ -745,19 +771,19 @@ static bool launch_pp(const PPPlan& p, const IgemmArgs& a0, hipStream_t st) {
     if (pp_strided(a)) {
       pp_fill_classes(a, p.bm);
       switch (p.variant) {
-        case PP_256x256: return pp_launch_one<2, 4, 4, 2, 2, 1, true>(grid, a, st);
-        case PP_128x256: return pp_launch_one<2, 4, 2, 2, 1, 1, true>(grid, a, st);
-        case PP_256x128: return pp_launch_one<4, 2, 2, 2, 1, 1, true>(grid, a, st);
-        case PP_512x128: return pp_launch_one<4, 2, 4, 2, 2, 1, true>(grid, a, st);
+        case PP_256x256: return pp_launch_one<2, 4, 4, 2, 2, 1, true, EPI>(grid, a, st);
+        case PP_128x256: return pp_launch_one<2, 4, 2, 2, 1, 1, true, EPI>(grid, a, st);
+        case PP_256x128: return pp_launch_one<4, 2, 2, 2, 1, 1, true, EPI>(grid, a, st);
+        case PP_512x128: return pp_launch_one<4, 2, 4, 2, 2, 1, true, EPI>(grid, a, st);
         default: return false;
       }
     }
   }
   switch (p.variant) {
-    case PP_256x256: return pp_launch_one<2, 4, 4, 2, 2, MODE>(grid, a, st);
-    case PP_128x256: return pp_launch_one<2, 4, 2, 2, 1, MODE>(grid, a, st);
-    case PP_256x128: return pp_launch_one<4, 2, 2, 2, 1, MODE>(grid, a, st);
-    case PP_512x128: return pp_launch_one<4, 2, 4, 2, 2, MODE>(grid, a, st);
+    case PP_256x256: return pp_launch_one<2, 4, 4, 2, 2, MODE, false, EPI>(grid, a, st);
+    case PP_128x256: return pp_launch_one<2, 4, 2, 2, 1, MODE, false, EPI>(grid, a, st);
+    case PP_256x128: return pp_launch_one<4, 2, 2, 2, 1, MODE, false, EPI>(grid, a, st);
+    case PP_512x128: return pp_launch_one<4, 2, 4, 2, 2, MODE, false, EPI>(grid, a, st);
     default: return false;
   }
 }
@@ -842,28 +868,33 @@ static bool pp_wgrad_launch(const PPBwdPlan& p, const WgradArgs& aw, hipStream_t
   RIGL_K_LAUNCH((k_wgrad_pp<2>), dim3(p.nw), dim3(512), (PPGeom<2, 4, 4, 2, 2>::SMEM), st, aw);
   return true;
 }
-template <int WMD, int WND, int TMD, int TND, int PHD, bool CLSD>
+template <int WMD, int WND, int TMD, int TND, int PHD, bool CLSD, int EPI = EPI_NONE>
 static bool pp_bwd_launch_one(const IgemmArgs& ad, const WgradArgs& aw, unsigned nd, unsigned nw, bool wgrad_first, hipStream_t st) {
   constexpr int SM_D = PPGeom<WMD, WND, TMD, TND, PHD>::SMEM, SM_W = PPGeom<2, 4, 4, 2, 2>::SMEM, SM = SM_D > SM_W ? SM_D : SM_W;
-  static const bool ready = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bwd_pp<WMD, WND, TMD, TND, PHD, CLSD>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, SM) == hipSuccess;
+  const void* k = EPI == EPI_RELU ? reinterpret_cast<const void*>(&k_bwd_pp_relu<WMD, WND, TMD, TND, PHD, CLSD>)
+                                  : reinterpret_cast<const void*>(&k_bwd_pp<WMD, WND, TMD, TND, PHD, CLSD>);
+  static const bool ready = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SM) == hipSuccess;
   if (!ready) return false;
-  RIGL_K_LAUNCH((k_bwd_pp<WMD, WND, TMD, TND, PHD, CLSD>), dim3(nd + nw), dim3(512), SM, st, ad, aw, nd, nw, (uint32_t)(wgrad_first ? 1u : 0u));
+  if constexpr (EPI == EPI_RELU)
+    RIGL_K_LAUNCH((k_bwd_pp_relu<WMD, WND, TMD, TND, PHD, CLSD>), dim3(nd + nw), dim3(512), SM, st, ad, aw, nd, nw, (uint32_t)(wgrad_first ? 1u : 0u));
+  else
+    RIGL_K_LAUNCH((k_bwd_pp<WMD, WND, TMD, TND, PHD, CLSD>), dim3(nd + nw), dim3(512), SM, st, ad, aw, nd, nw, (uint32_t)(wgrad_first ? 1u : 0u));
   return true;
 }
 // dvar = the dgrad tile (256 output columns: the weight gradient's 256-channel tiles imply cin % 256 == 0), strided =
 // parity-class dgrad
+template <int EPI = EPI_NONE>
 static bool pp_bwd_launch(int dvar, bool strided, const IgemmArgs& ad, const WgradArgs& aw, const PPBwdPlan& pw, hipStream_t st) {
   if (strided) {
     switch (dvar) {
-      case PP_256x256: return pp_bwd_launch_one<2, 4, 4, 2, 2, true>(ad, aw, pw.nd, pw.nw, pw.wgrad_first, st);
-      case PP_128x256: return pp_bwd_launch_one<2, 4, 2, 2, 1, true>(ad, aw, pw.nd, pw.nw, pw.wgrad_first, st);
+      case PP_256x256: return pp_bwd_launch_one<2, 4, 4, 2, 2, true, EPI>(ad, aw, pw.nd, pw.nw, pw.wgrad_first, st);
+      case PP_128x256: return pp_bwd_launch_one<2, 4, 2, 2, 1, true, EPI>(ad, aw, pw.nd, pw.nw, pw.wgrad_first, st);
       default: return false;
     }
   }
   switch (dvar) {
-    case PP_256x256: return pp_bwd_launch_one<2, 4, 4, 2, 2, false>(ad, aw, pw.nd, pw.nw, pw.wgrad_first, st);
-    case PP_128x256: return pp_bwd_launch_one<2, 4, 2, 2, 1, false>(ad, aw, pw.nd, pw.nw, pw.wgrad_first, st);
+    case PP_256x256: return pp_bwd_launch_one<2, 4, 4, 2, 2, false, EPI>(ad, aw, pw.nd, pw.nw, pw.wgrad_first, st);
+    case PP_128x256: return pp_bwd_launch_one<2, 4, 2, 2, 1, false, EPI>(ad, aw, pw.nd, pw.nw, pw.wgrad_first, st);
     default: return false;
   }
 }

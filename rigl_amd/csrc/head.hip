@@ -5,6 +5,7 @@
 // were 0.12 ms of pure launch latency.  Three kernels replace them:
 //   rigl_global_avgpool_fwd : y[n,c]   = bf16( sum_p float(x[n,p,c]) / P )          (fp32 accumulation)
 //   rigl_global_avgpool_bwd : dx[n,p,c] = bf16( float(dy[n,c]) / P )
+//   (rigl_global_avgpool_bwd_relu: the same times [x[n,p,c] > 0], the ReLU in front of the pool)
 //   rigl_softmax_xent       : per row  loss = -(sum_k t_k * log p_k),  t = onehot*(1-eps) + eps/K
 //                             dlogits  = bf16( (p - t) * scale )       (scale = 1/batch for the mean loss)
 // and for evaluation (imagenet_train_eval.py:596-615, metric_fn) one more:
@@ -75,6 +76,25 @@ __global__ __launch_bounds__(THREADS) void k_avgpool_bwd8(int n, int p, int c8, 
     o.x = f2bf(bf_lo(v.x) / inv) | (f2bf(bf_hi(v.x) / inv) << 16); o.y = f2bf(bf_lo(v.y) / inv) | (f2bf(bf_hi(v.y) / inv) << 16);
     o.z = f2bf(bf_lo(v.z) / inv) | (f2bf(bf_hi(v.z) / inv) << 16); o.w = f2bf(bf_lo(v.w) / inv) | (f2bf(bf_hi(v.w) / inv) << 16);
     dx[i] = o;
+  }
+}
+
+// The gradient through relu then the spatial mean (VGG's last conv, vgg.py:185-186): dx = bf16(dy / P) * [x > 0], x = the
+// ReLU's output the forward pooled -- the mask of the ReLU in front, read off its output.  The division is the one of
+// k_avgpool_bwd8 (the same bits where x > 0); every load is issued, only the store is guarded.
+__global__ __launch_bounds__(THREADS) void k_avgpool_bwd8_relu(int n, int p, int c8, const uint4* __restrict__ dy,
+                                                               const uint4* __restrict__ x, uint4* __restrict__ dx) {
+  const int64_t total = (int64_t)n * p * c8;
+  const float inv = (float)p;
+  for (int64_t i0 = (int64_t)blockIdx.x * THREADS; i0 < total; i0 += (int64_t)gridDim.x * THREADS) {
+    const int64_t i = i0 + threadIdx.x, c = i < total ? i : total - 1;
+    const int ch = (int)(c % c8);
+    const int img = (int)(c / ((int64_t)p * c8));
+    const uint4 v = dy[(int64_t)img * c8 + ch], xv = x[c];
+    uint4 o;
+    o.x = f2bf(bf_lo(v.x) / inv) | (f2bf(bf_hi(v.x) / inv) << 16); o.y = f2bf(bf_lo(v.y) / inv) | (f2bf(bf_hi(v.y) / inv) << 16);
+    o.z = f2bf(bf_lo(v.z) / inv) | (f2bf(bf_hi(v.z) / inv) << 16); o.w = f2bf(bf_lo(v.w) / inv) | (f2bf(bf_hi(v.w) / inv) << 16);
+    if (i < total) dx[i] = gate_bf16x8(o, xv);
   }
 }
 
@@ -272,6 +292,23 @@ int rigl_global_avgpool_bwd(int32_t n, int32_t pixels, int32_t c, const rigl_bf1
   hipLaunchKernelGGL(k_avgpool_bwd, dim3((unsigned)blocks), dim3(THREADS), 0, as_stream(stream), n, pixels, c2,
                      reinterpret_cast<const uint32_t*>(dy), reinterpret_cast<uint32_t*>(dx));
   RIGL_CHECK_LAUNCH("rigl_global_avgpool_bwd");
+  return RIGL_OK;
+}
+
+int rigl_global_avgpool_bwd_relu(int32_t n, int32_t pixels, int32_t c, const rigl_bf16* dy, const rigl_bf16* x, rigl_bf16* dx,
+                                 rigl_stream_t stream) {
+  using namespace rigl;
+  using namespace rigl::khead;
+  if (n <= 0 || pixels <= 0 || c <= 0 || (c & 7)) return fail(RIGL_EINVAL, "rigl_global_avgpool_bwd_relu: need n, pixels > 0 and c %% 8 == 0");
+  if (!dy || !x || !dx) return fail(RIGL_EINVAL, "rigl_global_avgpool_bwd_relu: NULL tensor");
+  if (((uintptr_t)dy & 15) || ((uintptr_t)x & 15) || ((uintptr_t)dx & 15))
+    return fail(RIGL_EINVAL, "rigl_global_avgpool_bwd_relu: tensors must be 16-byte aligned");
+  const int c8 = c / 8;
+  int64_t blocks = ((int64_t)n * pixels * c8 + THREADS - 1) / THREADS;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(k_avgpool_bwd8_relu, dim3((unsigned)blocks), dim3(THREADS), 0, as_stream(stream), n, pixels, c8,
+                     reinterpret_cast<const uint4*>(dy), reinterpret_cast<const uint4*>(x), reinterpret_cast<uint4*>(dx));
+  RIGL_CHECK_LAUNCH("rigl_global_avgpool_bwd_relu");
   return RIGL_OK;
 }
 

@@ -724,6 +724,85 @@ def conv_bwd_grid(d, x, dy, w_hwio, dw, on_dw_ready=None):
 # ----------------------------------------------------------------------------
 # K1 in fp32 arithmetic (validation twin; the reference's --precision=float32)
 # ----------------------------------------------------------------------------
+# ----------------------------------------------------------------------------
+# masked conv + ReLU without a batch norm (VGG)
+# ----------------------------------------------------------------------------
+def conv_fwd_takes_relu_epilogue(d):
+  """Does this layer's forward body carry the ReLU epilogue (rigl_conv2d_fwd_takes_relu_epilogue)?  Else conv_fwd_relu runs the
+  plain forward and the stand-alone relu pass -- the same bits."""
+  return bool(_plan_cached(d, 'fwd_relu_epi', lambda: int(_lib.load().rigl_conv2d_fwd_takes_relu_epilogue(C.byref(d)))))
+
+
+def conv_bwd_takes_relu_epilogue(d):
+  """Does this layer's dgrad body carry the ReLU gate (rigl_conv2d_bwd_takes_relu_epilogue)?"""
+  return bool(_plan_cached(d, 'bwd_relu_epi', lambda: int(_lib.load().rigl_conv2d_bwd_takes_relu_epilogue(C.byref(d)))))
+
+
+def conv_fwd_relu(d, x, w_ohwi, y=None):
+  """y = bf16(max(conv(x, w), 0)) (rigl_masked_conv2d_fwd_relu): the pre-activation is never stored."""
+  _req(x, torch.bfloat16, 'x')
+  _req(w_ohwi, torch.bfloat16, 'w_ohwi')
+  if x.numel() != d.n * d.h * d.w * d.cin:
+    raise ValueError('x must be [n, h, w, Cin] of the descriptor')
+  _count_macs('fwd_macs', d)
+  if y is None:
+    y = torch.empty((d.n, d.ho, d.wo, d.cout), dtype=torch.bfloat16, device=x.device)
+  _req(y, torch.bfloat16, 'y')
+  lib = _lib.load()
+  need = _plan_cached(d, 'ws_fwd', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 0))
+  ws = workspace(need, x.device) if need else None
+  check(lib.rigl_masked_conv2d_fwd_relu(C.byref(d), _ptr(x), _ptr(w_ohwi), _ptr(y), _ptr(ws),
+                                        ws.numel() if ws is not None else 0, _stream()))
+  return y
+
+
+def conv_bwd_relu(d, x, dy, w_hwio, dw, on_dw_ready=None):
+  """dW (dense fp32, into ``dw``) and dX = bf16(dgrad(dy)) * [x > 0] of a conv whose input ``x`` is a ReLU output (or a max
+  pool of one) -- rigl_masked_conv2d_bwd_relu.  ``dy`` must already carry this conv's own ReLU gate.  Returns dX."""
+  _req(x, torch.bfloat16, 'x')
+  _req(dy, torch.bfloat16, 'dy')
+  _req(w_hwio, torch.bfloat16, 'w_hwio')
+  _req(dw, torch.float32, 'dw')
+  if x.numel() != d.n * d.h * d.w * d.cin or dy.numel() != d.n * d.ho * d.wo * d.cout:
+    raise ValueError('x / dy must have the shapes of the descriptor')
+  lib = _lib.load()
+  _count_macs('wgrad_macs', d)
+  _count_macs('dgrad_macs', d)
+  need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
+  ws = workspace(need, x.device, 'wg') if need else None
+  dx = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=dy.device)
+  check(lib.rigl_masked_conv2d_bwd_relu(C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(dw), _ptr(dx), _ptr(ws),
+                                        ws.numel() if ws is not None else 0, _stream()))
+  if on_dw_ready is not None:
+    on_dw_ready()
+  return dx
+
+
+def relu_fwd(x, y=None):
+  """Stand-alone y = relu(x) on a bf16 tensor (rigl_relu_fwd; ``y`` may be ``x``)."""
+  _req(x, torch.bfloat16, 'x')
+  if y is None:
+    y = torch.empty_like(x)
+  _req(y, torch.bfloat16, 'y')
+  if y.numel() != x.numel():
+    raise ValueError('y must have the shape of x')
+  check(_lib.load().rigl_relu_fwd(x.numel(), _ptr(x), _ptr(y), _stream()))
+  return y
+
+
+def relu_bwd(dy, x, dx=None):
+  """Stand-alone dx = dy * [x > 0] on bf16 tensors (rigl_relu_bwd; ``dx`` may be ``dy``)."""
+  _req(dy, torch.bfloat16, 'dy')
+  _req(x, torch.bfloat16, 'x')
+  if dx is None:
+    dx = torch.empty_like(dy)
+  _req(dx, torch.bfloat16, 'dx')
+  if not dy.numel() == x.numel() == dx.numel():
+    raise ValueError('dy, x and dx must have one shape')
+  check(_lib.load().rigl_relu_bwd(dy.numel(), _ptr(dy), _ptr(x), _ptr(dx), _stream()))
+  return dx
+
+
 def conv_fwd_f32(d, x, w_hwio, mask_bits=None, y=None):
   """y[N,Ho,Wo,Cout] fp32 = conv(x, mask * W): fp32 NHWC activations, the fp32 master weights (flat HWIO) and the
   mask bitmap (None: dense), on the fp32 MFMA (rigl_masked_conv2d_fwd_f32)."""
@@ -1049,6 +1128,18 @@ def global_avgpool_bwd(dy, h, w):
   n, c = dy.shape
   dx = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=dy.device)
   check(_lib.load().rigl_global_avgpool_bwd(n, h * w, c, _ptr(dy), _ptr(dx), _stream()))
+  return dx
+
+
+def global_avgpool_bwd_relu(dy, x):
+  """dx = global_avgpool_bwd(dy) * [x > 0], x = the pooled [N, H, W, C] ReLU output (rigl_global_avgpool_bwd_relu)."""
+  _req(dy, torch.bfloat16, 'dy')
+  _req(x, torch.bfloat16, 'x')
+  n, h, w, c = x.shape
+  if tuple(dy.shape) != (n, c):
+    raise ValueError('dy must be [N, C] of x')
+  dx = torch.empty_like(x)
+  check(_lib.load().rigl_global_avgpool_bwd_relu(n, h * w, c, _ptr(dy), _ptr(x), _ptr(dx), _stream()))
   return dx
 
 

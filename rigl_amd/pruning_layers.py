@@ -130,6 +130,36 @@ class _MaskedConvFn(torch.autograd.Function):
     return dx, None, None, None, None, None, None
 
 
+class _MaskedConvReluFn(torch.autograd.Function):
+  """y = relu(conv(x, mask*W)) with no batch norm in between (VGG: conv2d_fixed_padding + tf.nn.relu, vgg.py:124-134) --
+  one node that saves only x; the pre-activation is never stored (rigl_masked_conv2d_fwd_relu).
+
+  Contract of the backward: ``dy`` arrives already gated by [y > 0].  Every consumer of y in a VGG graph does that: the
+  next conv of this kind (``gate_input``: its dX is bf16(dgrad) * [x > 0], x = y or a max pool of y -- at the pool winner
+  y equals the pooled value), or nn.global_avg_pool_relu.  With ``gate_input`` dX is gated the same way
+  (rigl_masked_conv2d_bwd_relu), else it is the plain dgrad (the first conv reads the images and needs none).  Dense dW
+  goes into the layer's slice of the gradient arena as for every other layer."""
+
+  @staticmethod
+  def forward(ctx, x, lv, desc, need_dx, gate_input):
+    ctx.lv, ctx.desc, ctx.need_dx, ctx.gate_input = lv, desc, need_dx, gate_input
+    ctx.save_for_backward(x)
+    return ops.conv_fwd_relu(desc, x, lv.ohwi)
+
+  @staticmethod
+  def backward(ctx, dy):
+    (x,) = ctx.saved_tensors
+    lv, d = ctx.lv, ctx.desc
+    dy = dy.contiguous()
+    sync = getattr(lv.weights.graph, 'grad_sync', None)
+    ready = (lambda: sync.notify_layer_grad_ready(lv.weights)) if sync is not None else None
+    if ctx.need_dx and ctx.gate_input:
+      dx = ops.conv_bwd_relu(d, x, dy, lv.hwio, lv.weights.grad.view(-1), on_dw_ready=ready)
+    else:
+      dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=ctx.need_dx, on_dw_ready=ready)
+    return dx, None, None, None, None
+
+
 class _MaskedConvForkFn(torch.autograd.Function):
   """(y, x') = (conv(x, mask*W), x): the conv plus an alias of its input for the
   tensor's OTHER consumer (a residual shortcut, or the next conv reading the
@@ -341,6 +371,21 @@ class MaskedConv2d(_Layer):
     if part.numel():
       y.bn_partials = part
     return y
+
+  def conv_relu(self, x, gate_input=True):
+    """relu(conv(x)) as one node (_MaskedConvReluFn; bf16 only).  ``gate_input``: x is a ReLU output (or a max pool of one)
+    and dX passes that ReLU's gradient on; the output's own consumer must gate its gradient likewise."""
+    if x.dim() != 4 or x.shape[-1] != self.cin:
+      raise ValueError('expected [N,H,W,%d], got %s' % (self.cin, tuple(x.shape)))
+    if x.dtype != torch.bfloat16:
+      raise NotImplementedError('conv_relu: bf16 activations only')
+    self.graph.refresh_shadows()
+    n, h, w, _ = x.shape
+    d = self.desc_for(n, h, w)
+    need_dx = self.need_input_grad and x.requires_grad
+    if not x.requires_grad:
+      x = x.detach().requires_grad_(True)  # keep the node so wgrad runs
+    return _MaskedConvReluFn.apply(x.contiguous(), self.vars, d, need_dx, bool(gate_input))
 
   def takes_bn_input(self, x):
     """Does this conv's forward take relu(bn(.)) of its input on its operand load (rigl_masked_conv2d_fwd_bnrelu)?  ``x`` = the

@@ -463,6 +463,30 @@ def global_avg_pool(x):
   return x.float().mean(dim=(1, 2)).to(x.dtype)
 
 
+class _GlobalAvgPoolReluFn(torch.autograd.Function):
+  """The spatial mean of a ReLU output whose gradient also passes that ReLU: dx = bf16(dy / P) * [x > 0]
+  (rigl_global_avgpool_bwd_relu) -- the gated gradient pruning_layers._MaskedConvReluFn expects from its consumer."""
+
+  @staticmethod
+  def forward(ctx, x):
+    from rigl_amd import ops  # pylint: disable=import-outside-toplevel
+    ctx.save_for_backward(x)
+    return ops.global_avgpool_fwd(x)
+
+  @staticmethod
+  def backward(ctx, dy):
+    from rigl_amd import ops  # pylint: disable=import-outside-toplevel
+    (x,) = ctx.saved_tensors
+    return ops.global_avgpool_bwd_relu(dy.contiguous(), x)
+
+
+def global_avg_pool_relu(x):
+  """tf.reduce_mean(relu_output, [1, 2]) (vgg.py:185-186) for the output of a MaskedConv2d.conv_relu: [N, H, W, C] -> [N, C]."""
+  if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[-1] % 8 == 0):
+    raise ValueError('global_avg_pool_relu: a bf16 [N, H, W, C] GPU tensor with C % 8 == 0')
+  return _GlobalAvgPoolReluFn.apply(x.contiguous())
+
+
 class _SoftmaxXentFn(torch.autograd.Function):
   """Mean cross entropy with label smoothing; the kernel leaves d(mean loss)/d(logits) next to the row losses."""
 

@@ -7,6 +7,7 @@ Topologies re-stated from the reference model files:
   MobileNet-v1     rigl/imagenet_resnet/mobilenetv1_model.py:156-342
   WideResNet       rigl/cifar_resnet/resnet_model.py:70-235
   MNIST MLP        rigl/mnist/mnist_train_eval.py:112-132
+  VGG-A/16/19      rigl/imagenet_resnet/vgg.py:57-200
 """
 from collections import OrderedDict, namedtuple
 
@@ -188,3 +189,52 @@ def mobilenet_v1_stat_layers(num_classes=1000):
     in_ch = f
   out.append(StatLayer('dense', 'final_dense', (1024, num_classes)))
   return out
+
+
+VGG_CFG = {'vgg_a': [1, 1, 2, 2, 2], 'vgg_16': [2, 2, 3, 3, 3], 'vgg_19': [2, 2, 4, 4, 4]}   # convs per stage (vgg.py:57-61)
+VGG_STAGE_FILTERS = (64, 128, 256, 512, 512)
+
+
+def vgg_convs(vgg_type, width=1.0):
+  """Yields (name, cin, cout) of the 3x3 convs in creation order.  TF-slim ``layers.repeat(net, n, fn, ..., scope='convS')``
+  opens the variable scope convS and names the i-th call convS/convS_i (1-based), all inside
+  tf.variable_scope(vgg_type): vgg_16/conv1/conv1_1, ..."""
+  if vgg_type not in VGG_CFG:
+    raise ValueError('unknown VGG type %r (one of %s)' % (vgg_type, sorted(VGG_CFG)))
+  cin = 3
+  for stage, (reps, f) in enumerate(zip(VGG_CFG[vgg_type], VGG_STAGE_FILTERS), start=1):
+    cout = int(f * width)
+    for i in range(1, reps + 1):
+      yield '%s/conv%d/conv%d_%d' % (vgg_type, stage, stage, i), cin, cout
+      cin = cout
+
+
+def vgg_masks(vgg_type='vgg_16', prune_last_layer=True, num_classes=1000, width=1.0):
+  """Every conv is masked (HWIO 3x3) and -- with prune_last_layer -- the fc8 1x1 conv (vgg.py:187-194)."""
+  d = OrderedDict()
+  c = None
+  for name, cin, cout in vgg_convs(vgg_type, width):
+    d[name + '/mask:0'] = (3, 3, cin, cout)
+    c = cout
+  if prune_last_layer:
+    d['%s/fc8/mask:0' % vgg_type] = (1, 1, c, num_classes)
+  return d
+
+
+def vgg_macs_per_image(vgg_type='vgg_16', image_size=224, num_classes=1000):
+  """Dense MACs per image of the convs (fwd), the part dgrad repeats (every conv but the first, which reads the images)
+  and fc8's: (conv_fwd, conv_dgrad, fc8)."""
+  fwd = dgrad = 0
+  hw = image_size
+  convs = list(vgg_convs(vgg_type))
+  stage_of = [int(n.split('/')[1][4:]) for n, _, _ in convs]
+  prev = 1
+  for k, ((_, cin, cout), st) in enumerate(zip(convs, stage_of)):
+    if st != prev:
+      hw //= 2
+      prev = st
+    m = 9 * cin * cout * hw * hw
+    fwd += m
+    if k:
+      dgrad += m
+  return fwd, dgrad, convs[-1][2] * num_classes
