@@ -713,6 +713,11 @@ int rigl_bn_relu_maxpool_bwd(const RiglConvDesc* d, const rigl_bf16* x,
  * -sum_k t_k log softmax(z)_k with t = onehot * (1 - eps) + eps / K, and --
  * when dlogits is given -- dlogits = bf16((softmax(z) - t) * grad_scale), the
  * gradient of grad_scale * sum_r row_loss[r] (grad_scale = 1 / rows for the mean).
+ * A label outside [0, classes) is not an error: as with tf.one_hot
+ * (imagenet_train_eval.py:569-581) its one-hot row is all zero, t = eps / K for
+ * every class, so row_loss is the smoothing term alone (0 when eps = 0) and
+ * dlogits = bf16((softmax(z) - eps / K) * grad_scale) -- loss and gradient of
+ * the same function.  rigl_eval_metrics reports the same row loss.
  * ---------------------------------------------------------------------- */
 int rigl_global_avgpool_fwd(int32_t n, int32_t pixels, int32_t c, const rigl_bf16* x,
                             rigl_bf16* y, rigl_stream_t stream);

@@ -143,9 +143,12 @@ __device__ __forceinline__ void xent_row(int k, const T* z, float* sh, float& m,
   sz = block_reduce(sz, false, sh);
 }
 // -sum_k t_k (z_k - m - lse) = (1-eps) * (lse - (z_lab - m)) + eps/K * (K * lse - sum_k (z_k - m)); lse = log sum exp of the
-// shifted logits, zl = z_lab - m (0 for a label out of range), sz = sum_k (z_k - m)
-__device__ __forceinline__ float xent_loss(float lse, float sz, float zl, int k, float on, float off) {
-  return on * (lse - zl) + off * ((float)k * lse - sz);
+// shifted logits, zl = z_lab - m, sz = sum_k (z_k - m).  A label outside [0, K) has an all-zero one-hot row (tf.one_hot,
+// imagenet_train_eval.py:569-581): t = eps/K everywhere, so the (1-eps) term is absent -- the function whose gradient
+// k_softmax_xent writes with t = off for every class of such a row.
+__device__ __forceinline__ float xent_loss(float lse, float sz, float zl, bool in_range, int k, float on, float off) {
+  const float smooth = off * ((float)k * lse - sz);
+  return in_range ? on * (lse - zl) + smooth : smooth;
 }
 
 // One workgroup per row.
@@ -161,8 +164,8 @@ __global__ __launch_bounds__(THREADS) void k_softmax_xent(int k, const uint16_t*
   const int64_t lab = labels[row];
   const float on = 1.f - eps, off = eps / (float)k;
   if (threadIdx.x == 0) {
-    const float zl = (lab >= 0 && lab < k) ? bf16_at(z, lab) - m : 0.f;
-    row_loss[row] = xent_loss(lse, sz, zl, k, on, off);
+    const bool inr = lab >= 0 && lab < k;
+    row_loss[row] = xent_loss(lse, sz, inr ? bf16_at(z, lab) - m : 0.f, inr, k, on, off);
   }
   if (dlogits) {
     uint16_t* g = dlogits + (int64_t)row * k;
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(THREADS) void k_eval_metrics(int k, const uint16_t*
     }
     const bool top1 = inr && bi == (int)lab;
     const bool topkh = inr && isfinite(zlab) && !nf && cnt < topk;
-    row_loss[row] = xent_loss(lse, sz, inr ? zlab - m : 0.f, k, 1.f - eps, eps / (float)k);
+    row_loss[row] = xent_loss(lse, sz, inr ? zlab - m : 0.f, inr, k, 1.f - eps, eps / (float)k);
     row_flags[row] = (top1 ? 1 : 0) | (topkh ? 2 : 0);
     if (counts) {
       atomicAdd(counts, 1ull);

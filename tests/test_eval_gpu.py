@@ -42,6 +42,7 @@ def _np_metrics(z, lab, k):
 
 
 def _np_xent(z, lab, eps):
+  """Targets as tf.one_hot builds them: a label out of range has an all-zero row, t = eps / c everywhere."""
   z = z.astype(np.float64)
   c = z.shape[1]
   m = z.max(1, keepdims=True)
@@ -106,7 +107,8 @@ def test_eval_metrics_kernel_matches_metric_fn(c, eps):
     if k == 5:
       assert tk[2] and not tk[3] and t1[0] and not t1[1] and not tk[4] and not tk[7] and not t1[10] and not tk[11]
       assert t1[9] == (lab[9] == 1)
-  fin = np.isfinite(z).all(1) & (lab >= 0) & (lab < c)
+  fin = np.isfinite(z).all(1)                     # labels out of range included: the smoothing term alone (tf.one_hot)
+  assert not ((lab[fin] >= 0) & (lab[fin] < c)).all()
   np.testing.assert_allclose(loss.cpu().numpy()[fin], _np_xent(z, lab, eps)[fin], rtol=2e-5, atol=1e-5)
 
 

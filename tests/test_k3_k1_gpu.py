@@ -11,7 +11,7 @@ torch = pytest.importorskip('torch')
 import torch.nn.functional as F  # noqa: E402
 
 from oracle import rigl_oracle as O  # noqa: E402
-from tests import convref  # noqa: E402
+from tests import convref, glue_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -108,11 +108,11 @@ def test_pack_weights(k, cout):
   hwio = torch.empty(k * cout, dtype=torch.bfloat16, device=DEV)
   ohwi = torch.empty(k * cout, dtype=torch.bfloat16, device=DEV)
   ops.pack_weights(tw, bits, k, cout, hwio, ohwi)
-  ref = _bf16_round(w * mask)
-  np.testing.assert_array_equal(hwio.float().cpu().numpy().reshape(k, cout), ref)
-  np.testing.assert_array_equal(ohwi.float().cpu().numpy().reshape(cout, k), ref.T)
+  ref_hwio, ref_ohwi = glue_ref.pack_weights_ref(w, mask)
+  np.testing.assert_array_equal(hwio.float().cpu().numpy().reshape(k, cout), ref_hwio.float().numpy())
+  np.testing.assert_array_equal(ohwi.float().cpu().numpy().reshape(cout, k), ref_ohwi.float().numpy())
   ops.pack_weights(tw, None, k, cout, hwio, None)       # no mask = dense
-  np.testing.assert_array_equal(hwio.float().cpu().numpy().reshape(k, cout), _bf16_round(w))
+  np.testing.assert_array_equal(hwio.float().cpu().numpy().reshape(k, cout), glue_ref.pack_weights_ref(w)[0].float().numpy())
 
 
 # ------------------------------------------------------------------ K1
