@@ -206,7 +206,7 @@ def _bn_bwd_reductions_case(case):
 
 
 @pytest.mark.parametrize('shape', [(2, 16, 16, 64), (3, 15, 13, 64), (2, 9, 12, 8), (1, 6, 6, 256), (4, 112, 112, 64),
-                                   (2, 7, 7, 32)])
+                                   (2, 7, 7, 32), (128, 112, 112, 64)])
 def test_bn_relu_maxpool_in_one_piece(shape):
   """relu(bn(x)) -> 3x3 / 2 'SAME' max pooling without the activated tensor (rigl_bn_relu_maxpool_fwd / _bwd, the
   ResNet stem's tail) against the three-kernel form it replaces (bn_fwd, maxpool_fwd; maxpool_bwd, bn_bwd): pooled
@@ -276,13 +276,13 @@ def test_bn_relu_maxpool_autograd_node_equals_the_two_nodes():
 
 
 @pytest.mark.parametrize('shape', [(4, 14, 14, 64), (2, 7, 7, 2048), (3, 9, 5, 16), (2, 28, 28, 256), (33, 3, 3, 40),
-                                   (8, 56, 56, 256)])
+                                   (8, 56, 56, 256), (128, 56, 56, 256), (128, 28, 28, 512), (128, 14, 14, 1024),
+                                   (128, 7, 7, 2048)])
 def test_two_batch_norms_meeting_in_one_add(shape):
   """relu(bn(x) + bn2(x2)) in one piece (rigl_bn_add_bn_fwd / _bwd, the projection-shortcut blocks) against the calls
   it replaces -- bn_fwd(x2) -> bn_fwd(x, residual) and bn_bwd(want_dres) -> bn_bwd(dres): same arithmetic in the same
   order, so output, ReLU bits, statistics, moving averages, both input gradients and all four parameter gradients are
-  compared bit for bit."""
-  from rigl_amd import ops
+  compared bit for bit.  The last four shapes are ResNet-50's projection blocks at batch 128."""
   gen = torch.Generator(device=DEV).manual_seed(sum(shape) + 7)
   c = shape[-1]
   x = (torch.randn(shape, generator=gen, device=DEV) * 1.7 + 0.3).to(torch.bfloat16)
@@ -290,6 +290,24 @@ def test_two_batch_norms_meeting_in_one_add(shape):
   dy = torch.randn(shape, generator=gen, device=DEV).to(torch.bfloat16)
   gamma, gamma2 = torch.rand(c, generator=gen, device=DEV) + 0.5, torch.rand(c, generator=gen, device=DEV) + 0.5
   beta, beta2 = torch.randn(c, generator=gen, device=DEV) * 0.3, torch.randn(c, generator=gen, device=DEV) * 0.3
+  _pair_equals_separate_calls(x, x2, dy, gamma, gamma2, beta, beta2)
+
+
+@pytest.mark.parametrize('shape', [(33, 3, 3, 40), (16, 28, 28, 184)])
+def test_two_batch_norms_meeting_in_one_add_on_edge_data(shape):
+  """The same comparison on tests/bn_ref.py's edge_tensor: all-zero, constant, offset, tiny, large, sparse and sentinel
+  channels on either side, gamma = 0, negative and 2^-10 among the scales."""
+  from tests import bn_ref
+  m, c = shape[0] * shape[1] * shape[2], shape[3]
+  x, dy, _, gamma, beta = (t.to(DEV) for t in bn_ref.edge_tensor(m, c, 11))
+  x2, _, _, gamma2, beta2 = (t.to(DEV) for t in bn_ref.edge_tensor(m, c, 12))
+  x2, gamma2 = x2.roll(3, dims=1).contiguous(), gamma2.roll(1)       # other classes meet in a channel
+  _pair_equals_separate_calls(x, x2, dy, gamma, gamma2, beta, beta2)
+
+
+def _pair_equals_separate_calls(x, x2, dy, gamma, gamma2, beta, beta2):
+  from rigl_amd import ops
+  c = x.shape[-1]
   mk = lambda: (torch.zeros(c, device=DEV), torch.ones(c, device=DEV))
   # separate calls
   (rm, rv), (rm2, rv2) = mk(), mk()
