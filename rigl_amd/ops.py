@@ -417,13 +417,14 @@ def mfma_dgrad_supported(d):
   return d.cout % 8 == 0 and d.cin % 8 == 0
 
 
-def conv_fwd(d, x, w_ohwi, y=None, force_ref=False, stats=False, *, scale_shift=None, residual=None, relu=False):
+def conv_fwd(d, x, w_ohwi, y=None, force_ref=False, stats=False, *, scale_shift=None, residual=None, relu=False, part=None):
   """y[N,Ho,Wo,Cout] (bf16, NHWC memory) = conv(x, w).  With ``stats`` returns
   (y, partials): fp32 [parts, 2, Cout] batch-norm partial sums of y left by the
   conv epilogue (None where the MFMA path does not apply).
   Eval: with ``scale_shift`` (fp32 [2, Cout], bn_infer_params) y = bf16(relu?(fmaf(conv, scale, shift) (+ residual))), the frozen
   batch norm in the forward's epilogue where the layer takes it (conv_fwd_takes_bn_epilogue), else the plain forward followed by
-  bn_apply -- the same bits either way."""
+  bn_apply -- the same bits either way.
+  ``part`` (optional, with ``stats``): the caller's fp32 [rigl_conv2d_stats_parts, 2, Cout] buffer for the partials."""
   if scale_shift is not None or residual is not None or relu:
     if scale_shift is None or stats or force_ref:
       raise ValueError('conv_fwd: residual / relu need scale_shift, and the eval epilogue leaves no statistics')
@@ -443,15 +444,38 @@ def conv_fwd(d, x, w_ohwi, y=None, force_ref=False, stats=False, *, scale_shift=
   need = _plan_cached(d, 'ws_fwd', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 0))
   d._stats_parts = _plan_cached(d, 'stats_parts', lambda: lib.rigl_conv2d_stats_parts(C.byref(d)))
   ws = workspace(need, x.device) if need else None
-  part = None
   if stats:
-    parts = d._stats_parts
-    part = torch.empty((parts, 2, d.cout), dtype=torch.float32, device=x.device)
+    part = _stats_out(part, d._stats_parts, d.cout, x.device)
+  else:
+    part = None
   check(lib.rigl_masked_conv2d_fwd_stats(
       C.byref(d), _ptr(x), _ptr(w_ohwi), _ptr(y), _ptr(part),
       part.numel() if part is not None else 0, _ptr(ws),
       ws.numel() if ws is not None else 0, _stream()))
   return (y, part) if stats else y
+
+
+def _stats_out(part, parts, c, device):
+  """The statistics buffer of a forward: the caller's (checked: fp32, exactly [parts, 2, c]) or a fresh one."""
+  if part is None:
+    return torch.empty((parts, 2, c), dtype=torch.float32, device=device)
+  _req(part, torch.float32, 'part')
+  if tuple(part.shape) != (parts, 2, c):
+    raise ValueError('part must be [%d, 2, %d]' % (parts, c))
+  return part
+
+
+def _out(t, shape, dtype, device, name):
+  """An output tensor: the caller's (checked: dtype, contiguous, the element count of ``shape``) or a fresh one."""
+  if t is None:
+    return torch.empty(shape, dtype=dtype, device=device)
+  _req(t, dtype, name)
+  n = 1
+  for s in shape:
+    n *= s
+  if t.numel() != n:
+    raise ValueError('%s must hold %d elements (%s)' % (name, n, 'x'.join(map(str, shape))))
+  return t
 
 
 def conv_fwd_takes_bn_input(d):
@@ -461,7 +485,7 @@ def conv_fwd_takes_bn_input(d):
   return bool(_plan_cached(d, 'fwd_bn_input', lambda: int(_lib.load().rigl_conv2d_fwd_takes_bn_input(C.byref(d)))))
 
 
-def conv_fwd_bnrelu(d, x_pre, saved, w_ohwi, a_out, y=None, stats=False, *, scale_shift=None, residual=None, relu=False):
+def conv_fwd_bnrelu(d, x_pre, saved, w_ohwi, a_out, y=None, stats=False, *, scale_shift=None, residual=None, relu=False, part=None):
   """y = conv(relu(bn(x_pre)), w) with the batch norm's apply pass on the operand load (rigl_masked_conv2d_fwd_bnrelu):
   ``saved`` = fp32 [4, Cin] (mean, invstd, scale, shift: bn_statistics), ``a_out`` (bf16, the shape of x_pre) receives
   relu(bn(x_pre)) as a side output.  Returns y or (y, partials) like conv_fwd.
@@ -487,10 +511,11 @@ def conv_fwd_bnrelu(d, x_pre, saved, w_ohwi, a_out, y=None, stats=False, *, scal
     y = torch.empty((d.n, d.ho, d.wo, d.cout), dtype=torch.bfloat16, device=x_pre.device)
   _req(y, torch.bfloat16, 'y')
   lib = _lib.load()
-  part = None
   if stats:
     parts = _plan_cached(d, 'stats_parts', lambda: lib.rigl_conv2d_stats_parts(C.byref(d)))
-    part = torch.empty((parts, 2, d.cout), dtype=torch.float32, device=x_pre.device)
+    part = _stats_out(part, parts, d.cout, x_pre.device)
+  else:
+    part = None
   check(lib.rigl_masked_conv2d_fwd_bnrelu(C.byref(d), _ptr(x_pre), _ptr(saved[2]), _ptr(a_out), _ptr(w_ohwi), _ptr(y), _ptr(part),
                                           part.numel() if part is not None else 0, None, 0, _stream()))
   return (y, part) if stats else y
@@ -607,7 +632,7 @@ def conv_bwd_takes_masked_addend(d):
 
 
 def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, bn_fuse=None, addend_sub=None,
-             addend_bits=None):
+             addend_bits=None, dx=None):
   """dW (into ``dw``, dense fp32) and -- when ``need_dx`` -- dX (+ ``addend``) of one conv with a single host
   transition and, for ordinary layers, a single launch (rigl_masked_conv2d_bwd) followed by the split-K reduce that
   completes dW.  ``on_dw_ready`` is called once dW's last kernel has been enqueued (the data-parallel exchange launches
@@ -616,7 +641,8 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
   reductions are computed in the dgrad epilogue (rigl_masked_conv2d_bwd_bn) and returned as
   ``bn_fuse['partials']`` (fp32 [parts, 2, Cin]) for bn_bwd; left unset where the layer's kernels cannot.
   ``addend_sub`` = (sh, sw): ``addend`` is the gradient of the subsampled view x[:, ::sh, ::sw, :] -- bf16
-  [n, ceil(h / sh), ceil(w / sw), cin] -- added at those pixels only (rigl_masked_conv2d_bwd_sub)."""
+  [n, ceil(h / sh), ceil(w / sw), cin] -- added at those pixels only (rigl_masked_conv2d_bwd_sub).
+  ``dx`` (optional, with ``need_dx``): the caller's bf16 [n, h, w, cin] tensor for dX instead of a fresh one."""
   if addend_sub is not None and tuple(addend_sub) == (1, 1):
     addend_sub = None
   if addend_bits is not None:
@@ -632,7 +658,7 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
     _count_macs('dgrad_macs', d)
     need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
     ws = workspace(need, x.device, 'wg') if need else None
-    dx = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=dy.device)
+    dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dy.device, 'dx')
     check(lib.rigl_masked_conv2d_bwd_masked(C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), _ptr(addend_bits), _ptr(dw),
                                             _ptr(dx), _ptr(ws), ws.numel() if ws is not None else 0, _stream()))
     if on_dw_ready is not None:
@@ -651,7 +677,7 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
     conv_wgrad(d, x, dy, dw)
     if on_dw_ready is not None:
       on_dw_ready()
-    return conv_dgrad(d, dy, w_hwio, addend=addend) if need_dx else None
+    return conv_dgrad(d, dy, w_hwio, dx=dx, addend=addend) if need_dx else None
   _req(x, torch.bfloat16, 'x')
   _req(dy, torch.bfloat16, 'dy')
   _req(dw, torch.float32, 'dw')
@@ -662,10 +688,11 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
     _count_macs('dgrad_macs', d)
   need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
   ws = workspace(need, x.device, 'wg') if need else None
-  dx = None
-  if need_dx:
+  if not need_dx:
+    dx = None
+  else:
     _req(w_hwio, torch.bfloat16, 'w_hwio')
-    dx = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=dy.device)
+    dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dy.device, 'dx')
     if addend is not None and addend_sub is None and addend.numel() != dx.numel():
       raise ValueError('addend must have the shape of dx')
   if addend_sub is not None:
@@ -699,7 +726,7 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
   return dx
 
 
-def conv_bwd_grid(d, x, dy, w_hwio, dw, on_dw_ready=None):
+def conv_bwd_grid(d, x, dy, w_hwio, dw, on_dw_ready=None, dx=None):
   """Backward of a strided 1x1 conv without padding with dX on the conv's own grid: returns bf16 [n, ho, wo, cin] -- the
   gradient at the pixels the conv read (zero elsewhere, never materialised) -- and writes the dense dW
   (rigl_masked_conv2d_bwd_grid).  The consumer is conv_bwd(..., addend=that, addend_sub=strides) of the tensor's other
@@ -713,7 +740,7 @@ def conv_bwd_grid(d, x, dy, w_hwio, dw, on_dw_ready=None):
   _count_macs('dgrad_macs', ConvDesc(d.n, d.ho, d.wo, d.cin, d.ho, d.wo, d.cout, 1, 1, 1, 1, 0, 0))
   need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
   ws = workspace(need, x.device, 'wg') if need else None
-  dx = torch.empty((d.n, d.ho, d.wo, d.cin), dtype=torch.bfloat16, device=dy.device)
+  dx = _out(dx, (d.n, d.ho, d.wo, d.cin), torch.bfloat16, dy.device, 'dx')      # (the caller's tensor, or a fresh one)
   check(lib.rigl_masked_conv2d_bwd_grid(C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(dw), _ptr(dx), _ptr(ws),
                                         ws.numel() if ws is not None else 0, _stream()))
   if on_dw_ready is not None:
@@ -756,7 +783,7 @@ def conv_fwd_relu(d, x, w_ohwi, y=None):
   return y
 
 
-def conv_bwd_relu(d, x, dy, w_hwio, dw, on_dw_ready=None):
+def conv_bwd_relu(d, x, dy, w_hwio, dw, on_dw_ready=None, dx=None):
   """dW (dense fp32, into ``dw``) and dX = bf16(dgrad(dy)) * [x > 0] of a conv whose input ``x`` is a ReLU output (or a max
   pool of one) -- rigl_masked_conv2d_bwd_relu.  ``dy`` must already carry this conv's own ReLU gate.  Returns dX."""
   _req(x, torch.bfloat16, 'x')
@@ -770,7 +797,7 @@ def conv_bwd_relu(d, x, dy, w_hwio, dw, on_dw_ready=None):
   _count_macs('dgrad_macs', d)
   need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
   ws = workspace(need, x.device, 'wg') if need else None
-  dx = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=dy.device)
+  dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dy.device, 'dx')        # (the caller's tensor, or a fresh one)
   check(lib.rigl_masked_conv2d_bwd_relu(C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(dw), _ptr(dx), _ptr(ws),
                                         ws.numel() if ws is not None else 0, _stream()))
   if on_dw_ready is not None:
@@ -817,7 +844,7 @@ def conv_fwd_f32(d, x, w_hwio, mask_bits=None, y=None):
   return y
 
 
-def conv_bwd_f32(d, x, dy, w_hwio, mask_bits, dw, need_dx=True, addend=None, on_dw_ready=None):
+def conv_bwd_f32(d, x, dy, w_hwio, mask_bits, dw, need_dx=True, addend=None, on_dw_ready=None, dx=None):
   """fp32 twin of conv_bwd: dense dW (fp32 HWIO, overwritten) and -- when ``need_dx`` -- dX (+ ``addend``)."""
   _req(x, torch.float32, 'x')
   _req(dy, torch.float32, 'dy')
@@ -836,7 +863,7 @@ def conv_bwd_f32(d, x, dy, w_hwio, mask_bits, dw, need_dx=True, addend=None, on_
     return None
   _count_macs('dgrad_macs', d)
   _req(w_hwio, torch.float32, 'w_hwio')
-  dx = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.float32, device=dy.device)
+  dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.float32, dy.device, 'dx')         # (the caller's tensor, or a fresh one)
   if addend is not None and addend.numel() != dx.numel():
     raise ValueError('addend must have the shape of dx')
   check(lib.rigl_masked_conv2d_dgrad_f32(C.byref(d), _ptr(dy), _ptr(w_hwio), _ptr(mask_bits), _ptr(addend), _ptr(dx),
@@ -847,29 +874,29 @@ def conv_bwd_f32(d, x, dy, w_hwio, mask_bits, dw, need_dx=True, addend=None, on_
 # ----------------------------------------------------------------------------
 # K1d depthwise
 # ----------------------------------------------------------------------------
-def depthwise_fwd(d, x, w, stats=False):
+def depthwise_fwd(d, x, w, stats=False, y=None, part=None):
   """y = depthwise conv(x, w).  With ``stats`` returns (y, partials): fp32 [parts, 2, C] batch-norm partial sums of y left
-  by the kernel's epilogue (None for shapes without one)."""
+  by the kernel's epilogue (None for shapes without one).  ``y`` / ``part`` (optional): the caller's output tensors."""
   _count_depthwise(d)
   _req(x, torch.bfloat16, 'x')
   _req(w, torch.float32, 'w')
-  y = torch.empty((d.n, d.ho, d.wo, d.cout), dtype=torch.bfloat16, device=x.device)
+  y = _out(y, (d.n, d.ho, d.wo, d.cout), torch.bfloat16, x.device, 'y')
   lib = _lib.load()
   if stats:
     parts = _plan_cached(d, 'dw_parts', lambda: int(lib.rigl_depthwise_conv2d_stats_parts(C.byref(d))))
     if parts > 0:
-      part = torch.empty((parts, 2, d.cout), dtype=torch.float32, device=x.device)
+      part = _stats_out(part, parts, d.cout, x.device)
       check(lib.rigl_depthwise_conv2d_fwd_stats(C.byref(d), _ptr(x), _ptr(w), _ptr(y), _ptr(part), part.numel(), _stream()))
       return y, part
   check(lib.rigl_depthwise_conv2d_fwd(C.byref(d), _ptr(x), _ptr(w), _ptr(y), _stream()))
   return (y, None) if stats else y
 
 
-def depthwise_dgrad(d, dy, w):
+def depthwise_dgrad(d, dy, w, dx=None):
   _count_depthwise(d)
   _req(dy, torch.bfloat16, 'dy')
   _req(w, torch.float32, 'w')
-  dx = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=dy.device)
+  dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dy.device, 'dx')
   check(_lib.load().rigl_depthwise_conv2d_dgrad(C.byref(d), _ptr(dy), _ptr(w), _ptr(dx), _stream()))
   return dx
 

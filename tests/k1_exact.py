@@ -1,0 +1,397 @@
+#!/usr/bin/env python3
+"""K1 exact runner (GPU): every conv entry point of the C ABI on tests/exactref.py's integer operands, against the BITS the
+documented arithmetic gives for the exact (fp64) result -- no tolerance -- with every output carved out of a sentinel-filled
+buffer (guard bands in front and behind, no element left unwritten).
+
+The kernel-selection knobs all have run-time twins (ops.tune_set), so one process walks a case list: per case and regime
+('low': nothing rounds, statistics partials add up exactly; 'round': outputs on bf16 ties) the operands and the fp64
+reference are made once, the input conditions (sum|a||b| <= 2^24 units, tie shares) are asserted on the reference, and then
+every setting of the set must reproduce the same expected bits -- so all bodies are bit-identical to each other as well.
+
+  python tests/k1_exact.py --set small          # k1_check.SMALL_CASES under test_k1_parity_gpu.PP_SETTINGS
+  python tests/k1_exact.py --set pp             # ... PP_CASES under the same settings
+  python tests/k1_exact.py --set stem | c3 | bs # default, and with the body's knob off
+  python tests/k1_exact.py --set rs             # rowstream = 2 / default / 0
+  python tests/k1_exact.py --set resnet50 --batch 128      # default and the all-generic setting
+  python tests/k1_exact.py --set mobilenet_v1 --batch 128  # default, rowstream = 2, all-generic
+  python tests/k1_exact.py --set vgg            # test_vgg_gpu's 3x3 shapes, with and without the fused ReLU
+  python tests/k1_exact.py --set dw | dw128     # depthwise: test_k3_k1_gpu's cases / MobileNet-v1's layers at batch 128
+  python tests/k1_exact.py --set f32            # the fp32 twin on test_k1_fp32_gpu.KERNEL_CASES, dense and masked
+
+Prints one line per case and regime and a final JSON verdict {"ok": true, "cases": n, "settings": m, "checks": c,
+"diff_bits": 0, "guards": "intact", "unwritten": 0, ...}; stops at the first failure with exit code 1.
+Test infrastructure: tests/test_k1_exact_gpu.py calls it in a subprocess, each under its own timeout.
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from tests import exactref as E  # noqa: E402
+from tests import k1_check  # noqa: E402
+
+DEV = 'cuda:0'
+BF, F32 = torch.bfloat16, torch.float32
+GENERIC = {'bwd1x1': 0, 'stem_direct': 0, 'wgrad_il': 0, 'c3x3': 0, 'rowstream': 0, 'bwdslice': 0}
+
+
+def _knobs(env):
+  """{'RIGL_PP_FWD': '1'} -> {'pp_fwd': 1}: an environment setting of the parity tests as its run-time twin."""
+  return {k[len('RIGL_'):].lower(): int(v) for k, v in env.items()}
+
+
+def settings_for(name):
+  if name in ('small', 'pp'):
+    from tests.test_k1_parity_gpu import PP_SETTINGS
+    return [_knobs(e) for e in PP_SETTINGS]
+  return {'stem': [{}, {'stem_direct': 0}], 'c3': [{}, {'c3x3': 0}], 'bs': [{}, {'bwdslice': 0}],
+          'rs': [{'rowstream': 2}, {}, {'rowstream': 0}], 'resnet50': [{}, GENERIC],
+          'mobilenet_v1': [{}, {'rowstream': 2}, GENERIC], 'vgg': [{'relu_fuse': 1}, {'relu_fuse': 0}],
+          'dw': [{}], 'dw128': [{}], 'f32': [{}]}[name]
+
+
+def cases_for(name, batch):
+  fixed = {'small': k1_check.SMALL_CASES, 'pp': k1_check.PP_CASES, 'stem': k1_check.STEM_CASES, 'c3': k1_check.C3_CASES,
+           'rs': k1_check.RS_CASES, 'bs': k1_check.BS_CASES}
+  if name in fixed:
+    return fixed[name]
+  if name == 'resnet50':
+    return k1_check.resnet50_shapes(batch)
+  if name == 'mobilenet_v1':
+    return k1_check.mobilenet_v1_shapes(batch)
+  if name == 'vgg':
+    from tests.test_vgg_gpu import C3_SHAPES, VGG16_SHAPES
+    return [(n, h, w, ci, co, 3, 1, 1, 1, h, w) for n, h, w, ci, co in VGG16_SHAPES + C3_SHAPES]
+  if name == 'f32':
+    from tests.test_k1_fp32_gpu import KERNEL_CASES
+    return [(n, h, w, ci, co, k, s, p, p, ho, wo) for n, h, w, ci, co, k, s, p, ho, wo in KERNEL_CASES]
+  from tests import test_k3_k1_gpu as T
+  if name == 'dw128':
+    return [(batch, hw, hw, c, c, 3, s, 1, 1, (hw - 1) // s + 1, (hw - 1) // s + 1) for hw, c, s in T.MOBILENET_V1_DEPTHWISE]
+  assert name == 'dw'
+  out = []
+  for c in next(m for m in T.test_depthwise_conv.pytestmark if m.name == 'parametrize').args[1]:
+    N, H, W, C, k, s = c[:6]
+    if len(c) > 6:                                 # TF SAME: out = ceil(in / s), the extra padding at the end
+      Ho, Wo = -(-H // s), -(-W // s)
+      pt, pl = max((Ho - 1) * s + k - H, 0) // 2, max((Wo - 1) * s + k - W, 0) // 2
+    else:
+      Ho, Wo, pt, pl = (H - 1) // s + 1, (W - 1) // s + 1, (k - 1) // 2, (k - 1) // 2
+    out.append((N, H, W, C, C, k, s, pt, pl, Ho, Wo))
+  return out
+
+
+class Tally:
+  checks = 0
+
+
+def _g(shape, dtype):
+  return E.guarded(shape, dtype, DEV)
+
+
+def _verify(name, out, check, want):
+  """Guards intact, nothing unwritten, and the output's bits == the expected bits."""
+  check(name)
+  E.assert_bits(name, E.got_bits(out), want)
+  Tally.checks += 1
+
+
+def _bf(t, what):
+  b = t.to(BF)
+  assert bool((b.float() == t).all()), '%s: an operand is not exact in bf16' % what
+  return b
+
+
+def _pack(op, ops):
+  """bf16 shadows through the product's own pack kernel (mask bits for every second seed), pinned to bf16(mask * w)."""
+  k, _, Cin, Cout = op.w.shape
+  n = op.w.numel()
+  hwio, chk_h, _ = _g((n,), BF)
+  ohwi, chk_o, _ = _g((n,), BF)
+  bits = ops.mask_pack(op.m01.reshape(-1).contiguous()) if op.m01 is not None else None
+  ops.pack_weights(op.w.reshape(-1).contiguous(), bits, k * k * Cin, Cout, hwio, ohwi)
+  want = E.rne_bits(op.wm.reshape(-1))
+  _verify('pack.hwio', hwio, chk_h, want)
+  _verify('pack.ohwi', ohwi, chk_o, want.reshape(k * k * Cin, Cout).t().contiguous())
+  return hwio, ohwi, bits
+
+
+def run_conv_case(case, seed, regime, settings):
+  from rigl_amd import _lib, ops
+  lib = _lib.load()
+  N, H, W, Cin, Cout, k, stride, pt, pl, Ho, Wo = case
+  op = E.operands(case, seed, regime, DEV)
+  x, dy, add = _bf(op.x, 'x'), _bf(op.dy, 'dy'), _bf(op.add, 'addend')
+  hwio, ohwi, _ = _pack(op, ops)
+  d = ops.conv_desc(N, H, W, Cin, Cout, k, k, stride, pt, pl, Ho, Wo)
+  has_dx = Cin % 8 == 0
+  ref, ab = E.reference(op, ('y', 'dx', 'dw') if has_dx else ('y', 'dw'))
+  fig = E.check_conditions(op, ref, ab)
+  del ab
+  n_w = k * k * Cin * Cout
+  # ---- the expected bits, once per case -------------------------------------------------------------------------------
+  want_y, want_dw = E.expect_plain(ref['y']), E.f32_pattern(ref['dw'].reshape(-1))
+  want_yr = E.expect_relu(ref['y'])
+  y2d = ref['y'].reshape(-1, Cout)
+  tot = (y2d.sum(0), (y2d * y2d).sum(0)) if regime == 'low' else None
+  if has_dx:
+    want_dx, want_dxa = E.expect_plain(ref['dx']), E.expect_acc(ref['dx'], op.add.double())
+    want_gate = E.expect_gate(ref['dx'], op.x)
+    addc = add[:, ::2, ::2, :].contiguous()
+    full = torch.zeros_like(op.add)
+    full[:, ::2, ::2, :] = op.add[:, ::2, ::2, :]
+    want_sub = E.expect_acc(ref['dx'], full.double())
+    del full
+    g = op.gen
+    m01 = torch.rand(add.numel(), generator=g, device=DEV) < 0.4
+    abits = torch.zeros(add.numel() // 8, dtype=torch.uint8, device=DEV)
+    for j in range(8):
+      abits |= (m01.view(-1, 8)[:, j].to(torch.uint8) << j)
+    want_msk = E.expect_acc(ref['dx'], torch.where(m01.view(op.add.shape), op.add, torch.zeros_like(op.add)).double())
+    del m01
+    grid = k == 1 and stride > 1 and pt == 0 and pl == 0 and Ho == -(-H // stride) and Wo == -(-W // stride)
+    want_grid = E.expect_plain(ref['dx'][:, ::stride, ::stride, :].contiguous()) if grid else None
+  fused = k == 1 and stride == 1 and Cout % 8 == 0 and has_dx
+  if fused:
+    # the eval epilogue: per-channel scale in +-1/2, +-1, +-2, integer shifts, an integer residual -- the fma is exact
+    ss = E.fused_params(op, Cout, op.uy, seed + 7)
+    res = E._ints((N, Ho, Wo, Cout), 64, 0.75, op.gen, DEV) * op.uy
+    res_b = _bf(res, 'residual')
+    want_ev = {(r, rl): E.expect_eval(ref['y'], ss[0].double(), ss[1].double(), res.double() if r else None, rl)
+               for r, rl in ((True, True), (False, False))}
+    # BN on load: a = bf16(relu(fma(x, scale, shift))) (exact: half-units of x), then the conv of it
+    ssi = E.fused_params(op, Cin, op.ux, seed + 11)
+    want_a = E.expect_bn_apply(op.x.double(), ssi[0].double(), ssi[1].double(), None, True)
+    a_val = E.bits_value(want_a).reshape(op.x.shape)
+    from tests import convref
+    ya = convref.conv_fp64(a_val, op.wm, op.dy, stride, pt, pl, Ho, Wo, ('y',))['y']
+    ya_ab = convref.conv_fp64(a_val.abs(), op.wm.abs(), op.dy, stride, pt, pl, Ho, Wo, ('y',))['y']
+    assert float(ya_ab.max()) / (op.uy / 2) <= E.LIMIT, 'BN on load: sum|a||w| over 2^24 half-units'
+    del ya_ab
+    want_ya = E.expect_plain(ya)
+    want_ya_ev = E.expect_eval(ya, ss[0].double(), ss[1].double(), res.double(), True)
+    saved = torch.cat([torch.zeros_like(ssi), ssi]).contiguous()          # [4, Cin]: rows 2-3 = scale, shift
+    del ya, a_val
+  del ref
+  # ---- every setting must reproduce them ------------------------------------------------------------------------------
+  for knobs in settings:
+    tag = lambda s: '%s [%s]' % (s, ' '.join('%s=%d' % kv for kv in sorted(knobs.items())) or 'default')   # noqa: E731
+    try:
+      for key, v in knobs.items():
+        ops.tune_set(key, v)
+      y, chk, _ = _g((N, Ho, Wo, Cout), BF)
+      ops.conv_fwd(d, x, ohwi, y=y)
+      _verify(tag('fwd'), y, chk, want_y)
+      if Cout % 8 == 0:
+        parts = int(lib.rigl_conv2d_stats_parts(ctypes.byref(d)))
+        y2, chk, _ = _g((N, Ho, Wo, Cout), BF)
+        part, chkp, _ = _g((parts, 2, Cout), F32)
+        _, p2 = ops.conv_fwd(d, x, ohwi, y=y2, stats=True, part=part)
+        assert p2 is part
+        _verify(tag('fwd_stats.y'), y2, chk, want_y)
+        chkp(tag('fwd_stats.part'))
+        if tot is not None:
+          s = part.double().sum(0)
+          assert torch.equal(s[0], tot[0]), tag('fwd_stats: the partials do not add up to the exact sum y')
+          assert torch.equal(s[1], tot[1]), tag('fwd_stats: the partials do not add up to the exact sum y^2')
+        Tally.checks += 1
+        del y2, part
+        yr, chk, _ = _g((N, Ho, Wo, Cout), BF)
+        ops.conv_fwd_relu(d, x, ohwi, y=yr)
+        _verify(tag('fwd_relu'), yr, chk, want_yr)
+        yr, chk, _ = _g((N, Ho, Wo, Cout), BF)
+        ops.relu_fwd(y, y=yr)
+        _verify(tag('relu_fwd(fwd)'), yr, chk, want_yr)
+        del yr
+      del y
+      dw, chk, _ = _g((n_w,), F32)
+      ops.conv_wgrad(d, x, dy, dw=dw)
+      _verify(tag('wgrad'), dw, chk, want_dw)
+      if not has_dx:
+        dw, chk, _ = _g((n_w,), F32)
+        assert ops.conv_bwd(d, x, dy, hwio, dw, need_dx=False) is None
+        _verify(tag('bwd.dw (no dX)'), dw, chk, want_dw)
+        continue
+      dx, chk, _ = _g((N, H, W, Cin), BF)
+      ops.conv_dgrad(d, dy, hwio, dx=dx)
+      _verify(tag('dgrad'), dx, chk, want_dx)
+      dxg, chkg, _ = _g((N, H, W, Cin), BF)
+      ops.relu_bwd(dx, x, dx=dxg)
+      _verify(tag('relu_bwd(dgrad)'), dxg, chkg, want_gate)
+      del dxg
+      dx, chk, _ = _g((N, H, W, Cin), BF)
+      ops.conv_dgrad(d, dy, hwio, dx=dx, addend=add)
+      _verify(tag('dgrad_acc'), dx, chk, want_dxa)
+      forms = [('bwd', dict(addend=add), want_dxa), ('bwd (no addend)', {}, want_dx),
+               ('bwd_sub', dict(addend=addc, addend_sub=(2, 2)), want_sub)]
+      if ops.conv_bwd_takes_masked_addend(d):
+        forms.append(('bwd_masked', dict(addend=add, addend_bits=abits), want_msk))
+      for nm, kw, want in forms:
+        dx, chk, _ = _g((N, H, W, Cin), BF)
+        dw, chkw, _ = _g((n_w,), F32)
+        assert ops.conv_bwd(d, x, dy, hwio, dw, need_dx=True, dx=dx, **kw) is dx
+        _verify(tag(nm + '.dx'), dx, chk, want)
+        _verify(tag(nm + '.dw'), dw, chkw, want_dw)
+      dx, chk, _ = _g((N, H, W, Cin), BF)
+      dw, chkw, _ = _g((n_w,), F32)
+      ops.conv_bwd_relu(d, x, dy, hwio, dw, dx=dx)
+      _verify(tag('bwd_relu.dx'), dx, chk, want_gate)
+      _verify(tag('bwd_relu.dw'), dw, chkw, want_dw)
+      if grid:
+        dxs, chk, _ = _g((N, Ho, Wo, Cin), BF)
+        dw, chkw, _ = _g((n_w,), F32)
+        ops.conv_bwd_grid(d, x, dy, hwio, dw, dx=dxs)
+        _verify(tag('bwd_grid.dx'), dxs, chk, want_grid)
+        _verify(tag('bwd_grid.dw'), dw, chkw, want_dw)
+        del dxs
+      del dx, dw
+      if fused:
+        for (r, rl), want in want_ev.items():
+          ye, chk, _ = _g((N, Ho, Wo, Cout), BF)
+          ops.conv_fwd(d, x, ohwi, y=ye, scale_shift=ss, residual=res_b if r else None, relu=rl)
+          _verify(tag('fwd_eval(residual=%d, relu=%d)' % (r, rl)), ye, chk, want)
+        ye, chk, _ = _g((N, Ho, Wo, Cout), BF)
+        ops.conv_fwd_bnrelu(d, x, ssi, ohwi, None, y=ye, scale_shift=ss, residual=res_b, relu=True)
+        _verify(tag('fwd_bnrelu eval'), ye, chk, want_ya_ev)
+        if ops.conv_fwd_takes_bn_input(d):
+          parts = int(lib.rigl_conv2d_stats_parts(ctypes.byref(d)))
+          ye, chk, _ = _g((N, Ho, Wo, Cout), BF)
+          a_out, chka, _ = _g((N, H, W, Cin), BF)
+          part, chkp, _ = _g((parts, 2, Cout), F32)
+          ops.conv_fwd_bnrelu(d, x, saved, ohwi, a_out, y=ye, stats=True, part=part)
+          _verify(tag('fwd_bnrelu.y'), ye, chk, want_ya)
+          _verify(tag('fwd_bnrelu.a_out'), a_out, chka, want_a)
+          chkp(tag('fwd_bnrelu.part'))
+          del a_out, part
+        del ye
+    finally:
+      for key in knobs:
+        ops.tune_unset(key)
+  torch.cuda.synchronize()
+  return fig
+
+
+def run_depthwise_case(case, seed, regime, settings):
+  from rigl_amd import _lib, ops
+  lib = _lib.load()
+  N, H, W, C, _, k, stride, pt, pl, Ho, Wo = case
+  op = E.operands(case, seed, regime, DEV, depthwise=True)
+  x, dy = _bf(op.x, 'x'), _bf(op.dy, 'dy')
+  wd = op.w.reshape(-1).contiguous()                 # fp32 [k, k, C], read directly (these layers are not masked)
+  d = ops.conv_desc(N, H, W, C, C, k, k, stride, pt, pl, Ho, Wo)
+  ref, ab = E.reference(op)
+  fig = E.check_conditions(op, ref, ab)
+  del ab
+  want_y, want_dx, want_dw = E.expect_plain(ref['y']), E.expect_plain(ref['dx']), E.f32_pattern(ref['dw'].reshape(-1))
+  y2d = ref['y'].reshape(-1, C)
+  tot = (y2d.sum(0), (y2d * y2d).sum(0)) if regime == 'low' else None
+  del ref
+  y, chk, _ = _g((N, Ho, Wo, C), BF)
+  ops.depthwise_fwd(d, x, wd, y=y)
+  _verify('depthwise fwd', y, chk, want_y)
+  parts = int(lib.rigl_depthwise_conv2d_stats_parts(ctypes.byref(d)))
+  if parts > 0:
+    y, chk, _ = _g((N, Ho, Wo, C), BF)
+    part, chkp, _ = _g((parts, 2, C), F32)
+    _, p2 = ops.depthwise_fwd(d, x, wd, stats=True, y=y, part=part)
+    assert p2 is part
+    _verify('depthwise fwd_stats.y', y, chk, want_y)
+    chkp('depthwise fwd_stats.part')
+    if tot is not None:
+      s = part.double().sum(0)
+      assert torch.equal(s[0], tot[0]), 'depthwise fwd_stats: the partials do not add up to the exact sum y'
+      assert torch.equal(s[1], tot[1]), 'depthwise fwd_stats: the partials do not add up to the exact sum y^2'
+    Tally.checks += 1
+  dx, chk, _ = _g((N, H, W, C), BF)
+  ops.depthwise_dgrad(d, dy, wd, dx=dx)
+  _verify('depthwise dgrad', dx, chk, want_dx)
+  dw, chk, _ = _g((k * k * C,), F32)
+  ops.depthwise_wgrad(d, x, dy, dw)
+  _verify('depthwise wgrad', dw, chk, want_dw)
+  torch.cuda.synchronize()
+  return fig
+
+
+def run_f32_case(case, seed, regime, settings):
+  """The fp32 twin: the same integers as fp32 tensors, the fp32 master weights with and without the mask bitmap; every
+  output is fp32 and exact, dX + addend included (one exact sum)."""
+  from rigl_amd import ops
+  N, H, W, Cin, Cout, k, stride, pt, pl, Ho, Wo = case
+  op = E.operands(case, seed | 1, regime, DEV)       # (an odd seed: the operands carry a mask; dense = the same w unmasked)
+  d = ops.conv_desc(N, H, W, Cin, Cout, k, k, stride, pt, pl, Ho, Wo)
+  bits = ops.mask_pack(op.m01.reshape(-1).contiguous())
+  n_w = op.w.numel()
+  fig = {}
+  for nm, mb, wm in (('masked', bits, op.wm), ('dense', None, op.w)):
+    op.wm = wm
+    ref, ab = E.reference(op)
+    if nm == 'masked':
+      fig = E.check_conditions(op, ref, ab)
+    else:
+      for key, unit in (('y', op.uy), ('dx', op.udx)):
+        assert float(ab[key].max()) / unit <= E.LIMIT, 'f32 dense: sum|a||b| over 2^24 units'
+    del ab
+    y, chk, _ = _g((N, Ho, Wo, Cout), F32)
+    ops.conv_fwd_f32(d, op.x, op.w.reshape(-1), mb, y=y)
+    _verify('fwd_f32 ' + nm, y, chk, E.f32_pattern(ref['y']))
+    dx, chk, _ = _g((N, H, W, Cin), F32)
+    dw, chkw, _ = _g((n_w,), F32)
+    ops.conv_bwd_f32(d, op.x, op.dy, op.w.reshape(-1), mb, dw, need_dx=True, addend=op.add, dx=dx)
+    _verify('bwd_f32.dx ' + nm, dx, chk, E.f32_pattern(ref['dx'] + op.add.double()))
+    _verify('bwd_f32.dw ' + nm, dw, chkw, E.f32_pattern(ref['dw'].reshape(-1)))
+    dx, chk, _ = _g((N, H, W, Cin), F32)
+    ops.conv_bwd_f32(d, op.x, op.dy, op.w.reshape(-1), mb, dw, need_dx=True, dx=dx)
+    _verify('bwd_f32.dx (no addend) ' + nm, dx, chk, E.f32_pattern(ref['dx']))
+    del ref
+  torch.cuda.synchronize()
+  return fig
+
+
+SETS = ['small', 'pp', 'stem', 'c3', 'rs', 'bs', 'resnet50', 'mobilenet_v1', 'vgg', 'dw', 'dw128', 'f32']
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--set', default='small', choices=SETS)
+  ap.add_argument('--batch', type=int, default=128)
+  ap.add_argument('--only', type=int, default=-1)
+  ap.add_argument('--regimes', default='low,round')
+  a = ap.parse_args()
+  cases, settings = cases_for(a.set, a.batch), settings_for(a.set)
+  run = run_depthwise_case if a.set in ('dw', 'dw128') else run_f32_case if a.set == 'f32' else run_conv_case
+  t0, n = time.time(), 0
+  cond = {'max_sum_ab': 0.0, 'min_ties': 1.0, 'min_ties_one_way': 1.0}
+  for i, c in enumerate(cases):
+    if a.only >= 0 and i != a.only:
+      continue
+    for regime in a.regimes.split(','):
+      try:
+        fig = run(c, 100 + i, regime, settings)
+      except AssertionError as e:
+        print('FAIL case %d %s %s: %s' % (i, c, regime, e), flush=True)
+        print(json.dumps({'ok': False, 'set': a.set, 'case': i, 'shape': list(c), 'regime': regime, 'error': str(e)[:600]}))
+        return 1
+      for key, v in fig.items():
+        if key.startswith('sum_ab_'):
+          cond['max_sum_ab'] = max(cond['max_sum_ab'], v)
+        if key.startswith('ties_'):
+          cond['min_ties'] = min(cond['min_ties'], v[0])
+          cond['min_ties_one_way'] = min(cond['min_ties_one_way'], v[1], v[2])
+      print('ok case %d %s %s %s' % (i, c, regime, json.dumps(fig)), flush=True)
+      torch.cuda.empty_cache()
+    n += 1
+  print(json.dumps({'ok': True, 'set': a.set, 'cases': n, 'regimes': a.regimes.split(','), 'settings': len(settings),
+                    'checks': Tally.checks, 'diff_bits': 0, 'guards': 'intact', 'unwritten': 0, 'conditions': cond,
+                    'seconds': round(time.time() - t0, 1)}))
+  return 0
+
+
+if __name__ == '__main__':
+  sys.exit(main())
