@@ -446,13 +446,37 @@ int rigl_masked_conv2d_bwd_sub(const RiglConvDesc* d, const rigl_bf16* x,
  * autodiff): the batch norm's backward hands its output gradient over as it is,
  * with the ReLU bits its forward left, and never writes the masked copy.  Only for
  * the layers rigl_conv2d_bwd_takes_masked_addend says 1 for (the channel-sliced
- * single-pass backward, bwdslice.hpp); RIGL_EUNSUPPORTED otherwise.            */
+ * single-pass backward, bwdslice.hpp, and the 256 <- 64 row-streaming dgrad,
+ * rowstream.hpp MODE 3, from 65 536 rows on -- knob "rs_masked_addend" = 2: from
+ * the 4 096 rows that body takes, 0: never) and, beyond the query, every layer
+ * whose row-streaming dgrad has the masked form; RIGL_EUNSUPPORTED otherwise.  */
 int32_t rigl_conv2d_bwd_takes_masked_addend(const RiglConvDesc* d);
 int rigl_masked_conv2d_bwd_masked(const RiglConvDesc* d, const rigl_bf16* x,
                                   const rigl_bf16* dy, const rigl_bf16* w_hwio,
                                   const rigl_bf16* addend, const uint8_t* addend_bits,
                                   float* dw, rigl_bf16* dx, void* workspace,
                                   size_t workspace_bytes, rigl_stream_t stream);
+
+/* rigl_masked_conv2d_bwd of the conv IN FRONT of a batch norm (+ shortcut,
+ * ReLU) whose backward apply pass is not run: `dout` is the gradient w.r.t.
+ * relu(bn(y) + shortcut) and the kernel forms
+ *   dy = bf16(a * (dz - b - xhat * c)),  dz = bit ? dout : 0,
+ *   xhat = (y - mean) * invstd
+ * on its operand load from dout, y (this conv's forward output), relu_bits
+ * (rigl_bn_fwd_stats) and mean / invstd / coef[3][cout] (rigl_bn_bwd_reduce) --
+ * the tensor rigl_bn_bwd would have written for this conv to read back once.
+ * dX and dW are bit-identical to rigl_bn_bwd followed by rigl_masked_conv2d_bwd.
+ * Only the layers rigl_conv2d_bwd_takes_bn_apply says 1 for (bwd1x1.hpp: 1x1,
+ * 64 -> 256, the row counts of the single-pass kernel; knob "bn_bwd_on_load" 0:
+ * none); RIGL_EUNSUPPORTED otherwise.                                          */
+int32_t rigl_conv2d_bwd_takes_bn_apply(const RiglConvDesc* d);
+int rigl_masked_conv2d_bwd_bnapply(const RiglConvDesc* d, const rigl_bf16* x,
+                                   const rigl_bf16* dout, const rigl_bf16* w_hwio,
+                                   const rigl_bf16* addend /* nullable */, float* dw,
+                                   rigl_bf16* dx, void* workspace, size_t workspace_bytes,
+                                   const rigl_bf16* y, const uint8_t* relu_bits,
+                                   const float* mean, const float* invstd,
+                                   const float* coef, rigl_stream_t stream);
 
 /* rigl_masked_conv2d_bwd with the BATCH-NORM BACKWARD REDUCTIONS of the
  * tensor dX is the gradient of riding in the dgrad epilogue.  In the reference every
@@ -594,6 +618,16 @@ int rigl_bn_bwd(int64_t m, int32_t c, const rigl_bf16* x,
                 rigl_bf16* dresidual /* nullable */, float* dgamma,
                 float* dbeta, void* workspace, size_t workspace_bytes,
                 rigl_stream_t stream);
+/* rigl_bn_bwd without its apply launch: reduce + finalize, leaving dgamma,
+ * dbeta and coef[3][c] (a = gamma * invstd, b = mean dz, c = mean dz * xhat) for
+ * the consumer that applies dx = a * (dz - b - xhat * c) on its own operand load
+ * (rigl_masked_conv2d_bwd_bnapply).  Same geometry and bits as rigl_bn_bwd's.   */
+int rigl_bn_bwd_reduce(int64_t m, int32_t c, const rigl_bf16* x,
+                       const uint8_t* relu_bits /* required with relu */,
+                       const rigl_bf16* dy, const float* gamma, const float* save_mean,
+                       const float* save_invstd, int32_t relu, float* dgamma,
+                       float* dbeta, float* coef, void* workspace,
+                       size_t workspace_bytes, rigl_stream_t stream);
 /* rigl_bn_bwd whose reduction pass is replaced by the producer's partial sums:
  * stats = [stats_parts][2][c] (sum dz, sum dz * xhat) from the dgrad epilogue
  * that wrote dy (rigl_masked_conv2d_bwd_bn); stats == NULL: plain rigl_bn_bwd. */

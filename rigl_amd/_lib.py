@@ -138,6 +138,8 @@ SIGNATURES = {
     'rigl_masked_conv2d_bwd': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     'rigl_masked_conv2d_bwd_masked': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     'rigl_conv2d_bwd_takes_masked_addend': (_I32, [C.POINTER(ConvDesc)]),
+    'rigl_conv2d_bwd_takes_bn_apply': (_I32, [C.POINTER(ConvDesc)]),
+    'rigl_masked_conv2d_bwd_bnapply': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     'rigl_masked_conv2d_bwd_grid': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _SZ, _P]),
     'rigl_masked_conv2d_bwd_sub': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _SZ, _P]),
     'rigl_masked_conv2d_wgrad': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P,
@@ -160,6 +162,7 @@ SIGNATURES = {
     'rigl_bn_fwd_stats': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _F, _F, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _SZ, _P]),
     'rigl_bn_bwd': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     'rigl_bn_bwd_stats': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P]),
+    'rigl_bn_bwd_reduce': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     'rigl_crc32c': (C.c_uint32, [_P, _SZ, C.c_uint32]),
     'rigl_stateless_random': (C.c_int, [_P, _I64, _I32, _I32, _I32, _F, _F, _P]),
     'rigl_stateless_random_batched': (C.c_int, [C.POINTER(RandomItem), _I32, _P]),

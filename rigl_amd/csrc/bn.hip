@@ -351,8 +351,7 @@ __global__ __launch_bounds__(THREADS) void k_bwd_apply(Geom G, const uint16_t* _
       bool on = true;
       if (RELU) on = MSK == 1 ? (yv[j] > 0.f) : (MSK == 2 ? ((mb >> j) & 1u) != 0u : (fmaf(xv[j], psc[j], psh[j]) > 0.f));
       const float dz = on ? dv[j] : 0.f;
-      const float xh = (xv[j] - pm[j]) * pis[j];
-      o[j] = pa[j] * (dz - pb[j] - xh * pc[j]);
+      o[j] = bn_bwd_dx(dz, xv[j], pm[j], pis[j], pa[j], pb[j], pc[j]);
       z[j] = dz;
     }
     uint4 out;
@@ -808,15 +807,17 @@ int rigl_bn_add_bn_bwd(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16
   return RIGL_OK;
 }
 
-int rigl_bn_bwd_stats(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16* y, const uint8_t* relu_bits,
-                      const rigl_bf16* dy, const float* gamma,
-                      const float* save_mean, const float* save_invstd, const float* save_scale, const float* save_shift,
-                      int32_t relu, rigl_bf16* dx, rigl_bf16* dresidual, float* dgamma, float* dbeta,
-                      const float* stats, int32_t stats_parts, void* workspace,
-                      size_t workspace_bytes, rigl_stream_t stream) {
+// rigl_bn_bwd_stats, or (coef_out given: rigl_bn_bwd_reduce) its reduce + finalize alone with the coefficients left in the
+// caller's tensor instead of the workspace -- the same two launches on the same geometry either way.
+static int bn_bwd_impl(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16* y, const uint8_t* relu_bits,
+                       const rigl_bf16* dy, const float* gamma,
+                       const float* save_mean, const float* save_invstd, const float* save_scale, const float* save_shift,
+                       int32_t relu, rigl_bf16* dx, rigl_bf16* dresidual, float* dgamma, float* dbeta,
+                       const float* stats, int32_t stats_parts, float* coef_out, void* workspace,
+                       size_t workspace_bytes, rigl_stream_t stream) {
   using namespace rigl;
   using namespace rigl::kbn;
-  if (m <= 0 || c <= 0 || !x || !dy || !gamma || !save_mean || !save_invstd || !dx || !dgamma || !dbeta)
+  if (m <= 0 || c <= 0 || !x || !dy || !gamma || !save_mean || !save_invstd || (!dx && !coef_out) || !dgamma || !dbeta)
     return fail(RIGL_EINVAL, "rigl_bn_bwd: bad arguments");
   if (c % 8) return fail(RIGL_EUNSUPPORTED, "rigl_bn_bwd: channels %% 8 != 0");
   if (relu && !y && !relu_bits && (!save_scale || !save_shift))
@@ -828,7 +829,7 @@ int rigl_bn_bwd_stats(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16*
   hipStream_t st = as_stream(stream);
   Geom g = make_geom(m, c);
   float* partial = static_cast<float*>(workspace);
-  float* coef = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)g.parts * 2 * c * 4, 256));
+  float* coef = coef_out ? coef_out : reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)g.parts * 2 * c * 4, 256));
   dim3 rgrid((unsigned)g.parts, (unsigned)((g.cg + g.tpr - 1) / g.tpr));
   const int msk = relu_bits ? 2 : (y ? 1 : 0);
   const float* red = partial;
@@ -851,6 +852,10 @@ int rigl_bn_bwd_stats(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16*
   else
     hipLaunchKernelGGL(k_bwd_finalize<16>, dim3((unsigned)((c + 15) / 16)), dim3(THREADS), 0, st, g, red, gamma,
                        save_invstd, dgamma, dbeta, coef);
+  if (coef_out) {                 // (the apply pass belongs to the consumer of dx: rigl_masked_conv2d_bwd_bnapply)
+    RIGL_CHECK_LAUNCH("rigl_bn_bwd_reduce");
+    return RIGL_OK;
+  }
   dim3 agrid(apply_grid(g));
   const size_t lds = g.fixed ? 0 : (size_t)7 * c * 4;
 #define RIGL_BWD_APPLY(R, K, D) hipLaunchKernelGGL((k_bwd_apply<R, K, D>), agrid, dim3(THREADS), lds, st, g, x, y, relu_bits, dy, save_mean, save_invstd, save_scale, save_shift, coef, dx, dresidual)
@@ -862,6 +867,27 @@ int rigl_bn_bwd_stats(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16*
 #undef RIGL_BWD_APPLY
   RIGL_CHECK_LAUNCH("rigl_bn_bwd");
   return RIGL_OK;
+}
+
+int rigl_bn_bwd_stats(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16* y, const uint8_t* relu_bits,
+                      const rigl_bf16* dy, const float* gamma,
+                      const float* save_mean, const float* save_invstd, const float* save_scale, const float* save_shift,
+                      int32_t relu, rigl_bf16* dx, rigl_bf16* dresidual, float* dgamma, float* dbeta,
+                      const float* stats, int32_t stats_parts, void* workspace,
+                      size_t workspace_bytes, rigl_stream_t stream) {
+  return bn_bwd_impl(m, c, x, y, relu_bits, dy, gamma, save_mean, save_invstd, save_scale, save_shift, relu, dx, dresidual, dgamma,
+                     dbeta, stats, stats_parts, nullptr, workspace, workspace_bytes, stream);
+}
+
+// rigl_bn_bwd without its apply launch: reduce + finalize, leaving dgamma, dbeta and coef[3][C] (a = gamma * invstd, b = mean dz,
+// c = mean dz * xhat) for a consumer that applies dx = a * (dz - b - xhat * c) itself (rigl_masked_conv2d_bwd_bnapply).
+int rigl_bn_bwd_reduce(int64_t m, int32_t c, const rigl_bf16* x, const uint8_t* relu_bits, const rigl_bf16* dy, const float* gamma,
+                       const float* save_mean, const float* save_invstd, int32_t relu, float* dgamma, float* dbeta, float* coef,
+                       void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
+  if (!coef) return rigl::fail(RIGL_EINVAL, "rigl_bn_bwd_reduce: coef is required");
+  if (relu && !relu_bits) return rigl::fail(RIGL_EINVAL, "rigl_bn_bwd_reduce: relu needs relu_bits");
+  return bn_bwd_impl(m, c, x, nullptr, relu ? relu_bits : nullptr, dy, gamma, save_mean, save_invstd, nullptr, nullptr, relu, nullptr,
+                     nullptr, dgamma, dbeta, nullptr, 0, coef, workspace, workspace_bytes, stream);
 }
 
 int rigl_bn_bwd(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16* y, const uint8_t* relu_bits,

@@ -30,6 +30,12 @@ struct Bwd1x1Args {
   float* SLAB;          // [splits][CI][CO] fp32 partial dW (NULL with DO_W = false)
   int M, splits, interleave;
   uint32_t x_bytes, dy_bytes;
+  // BNA kernels (below): DY is the gradient w.r.t. the OUTPUT of the batch norm (+ shortcut, ReLU) behind this conv
+  const uint16_t* Y3;   // [M][CO] bf16, this conv's forward output = the batch norm's input
+  const uint8_t* BITS;  // [M][CO / 8] the ReLU bits k_fwd_apply left (bit j of byte g = channel 8 g + j)
+  const float* MEAN;    // [CO]
+  const float* INVSTD;  // [CO]
+  const float* COEF;    // [3][CO] a, b, c of k_bwd_finalize
 };
 
 template <int ROWB>
@@ -40,17 +46,33 @@ __device__ __forceinline__ int dual_swz(int row) {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-template <int CI, int CO, bool DO_W, int NST>
-struct Bwd1x1Smem { static constexpr int BYTES = NST * 32 * ((DO_W ? CI : 0) + CO) * 2 + (CI <= 64 ? 2 : 1) * 32 * (CI * 2 + 16); };
-template <int CI, int CO, bool DO_W, int NST>
+// BNA ("bn_bwd_on_load"): the batch norm behind this conv runs its backward APPLY here, on the dY tile in LDS.  P.DY is then
+// dout, the gradient w.r.t. relu(bn3(y3) + shortcut); a stage also receives the y3 tile (same rows, same swizzled slots) and
+// the rows' ReLU bits, and before the K-tile's barrier every lane replaces the dout pieces its OWN wave's DMA brought in by
+//   dy3 = bf16(a * (dz - b - xhat * c)),  dz = bit ? dout : 0,  xhat = (y3 - mean) * invstd        (bn_bwd_dx, common.hpp)
+// -- what k_bwd_apply would have written to HBM for this kernel to read back.  A wave's vmcnt wait covers all 64 lanes of its
+// DMA instructions, so the pieces (and the bit bytes, which one dword DMA per wave brings for the wave's eight rows) are in LDS
+// when the wave's wait returns: no extra barrier.  A lane's pieces of a tile are four rows of ONE 8-channel chunk (the 512-byte
+// swizzle only uses the row bits lane / 32 and wave supply), so its 8 x 5 parameters stay in registers for the whole kernel.
+// Everything behind the barrier is the plain kernel.  A stage is 16 + 16 + 1 + 4 = 37 KB: one workgroup per CU with a four-deep
+// ring keeps 111 KB per CU in flight (plain kernel: 2 workgroups x 2 tiles x 20 KB = 80 KB); the grid, the K-tile -> workgroup
+// map and the slab order are the plain kernel's, so dW has its bits.
+template <int CI, int CO, bool DO_W, int NST, bool BNA = false>
+struct Bwd1x1Smem {
+  static constexpr int BYTES = NST * (32 * ((DO_W ? CI : 0) + CO) * 2 + (BNA ? 32 * CO * 2 + 32 * (CO / 8) : 0)) + (CI <= 64 ? 2 : 1) * 32 * (CI * 2 + 16);
+};
+template <int CI, int CO, bool DO_W, int NST, bool BNA = false>
 __global__ __launch_bounds__(THREADS) void k_bwd1x1(Bwd1x1Args P) {
   constexpr int PX = 32;
   constexpr int YROWB = CO * 2, XROWB = CI * 2;
-  constexpr int Y_BYTES = PX * YROWB, X_BYTES = DO_W ? PX * XROWB : 0, STAGE = Y_BYTES + X_BYTES;
+  constexpr int Y_BYTES = PX * YROWB, X_BYTES = DO_W ? PX * XROWB : 0;
+  constexpr int B_BYTES = BNA ? PX * (CO / 8) : 0;            // BNA: the tile's ReLU bits, 256 bytes per wave
+  constexpr int Y3_OFF = Y_BYTES + X_BYTES, B_OFF = Y3_OFF + (BNA ? Y_BYTES : 0), STAGE = B_OFF + B_BYTES;
+  static_assert(!BNA || (YROWB == 512 && B_BYTES == 4 * 256), "BNA: 256 output channels (a lane's pieces share one channel chunk)");
   constexpr int YI = YROWB / 32, XI = XROWB / 32;             // DMA wave-instructions per tile (1 KB each)
   constexpr int YPW = YI / 4 > 0 ? YI / 4 : 1, XPW = XI / 4 > 0 ? XI / 4 : 1;   // per wave
   static_assert(YI % 4 == 0 && XI % 4 == 0, "tiles are whole rounds of four waves");
-  constexpr int L = YPW + (DO_W ? XPW : 0);                  // DMA instructions per thread per K-tile
+  constexpr int L = YPW + (DO_W ? XPW : 0) + (BNA ? YPW + 1 : 0);   // DMA instructions per thread per K-tile
   constexpr int CF = CI / 16, CFW = CF / 2;                  // dgrad: 16-channel fragments, per wave (2 pixel fragments x 2 wave columns)
   constexpr int KSD = CO / 32;                               // dgrad k-steps (output channels, 32 per MFMA)
   constexpr int NFI = CI / 32, NFO = CO / 32;                // wgrad: 32x32 fragments of dW
@@ -67,7 +89,7 @@ __global__ __launch_bounds__(THREADS) void k_bwd1x1(Bwd1x1Args P) {
   constexpr bool DXDB = CI <= 64;
   constexpr int NDX = DXDB ? 2 : 1;
   constexpr int DXROWB = XROWB + 16, DX_BYTES = PX * DXROWB;
-  static_assert(NST * STAGE + NDX * DX_BYTES == Bwd1x1Smem<CI, CO, DO_W, NST>::BYTES, "host and device agree on the LDS size");
+  static_assert(NST * STAGE + NDX * DX_BYTES == Bwd1x1Smem<CI, CO, DO_W, NST, BNA>::BYTES, "host and device agree on the LDS size");
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   unsigned char* const dxs = smem + NST * STAGE;
 
@@ -84,6 +106,9 @@ __global__ __launch_bounds__(THREADS) void k_bwd1x1(Bwd1x1Args P) {
   const __amdgpu_buffer_rsrc_t rsrcY = make_rsrc(P.DY, P.dy_bytes), rsrcX = make_rsrc(P.X, P.x_bytes);
   const u32x4 rsrcY4 = make_rsrc4(P.DY, P.dy_bytes), rsrcX4 = make_rsrc4(P.X, P.x_bytes);
   (void)rsrcY4; (void)rsrcX4; (void)rsrcY; (void)rsrcX;
+  const u32x4 rsrcZ4 = make_rsrc4(BNA ? P.Y3 : P.DY, BNA ? P.dy_bytes : 0u);
+  const u32x4 rsrcB4 = make_rsrc4(BNA ? (const void*)P.BITS : (const void*)P.DY, BNA ? P.dy_bytes >> 4 : 0u);
+  (void)rsrcZ4; (void)rsrcB4;
 
   // ---- DMA lanes ------------------------------------------------------------------------------------------------------
   // wave-instruction i of a tile with ROWB-byte rows fills rows i * (1024 / ROWB) ..; lane l: row + l / (ROWB / 16),
@@ -99,6 +124,19 @@ __global__ __launch_bounds__(THREADS) void k_bwd1x1(Bwd1x1Args P) {
     const int i = q * 4 + wave, row = i * (1024 / XROWB) + lane / (XROWB / 16), slot = lane % (XROWB / 16);
     x_row[q] = row; x_col[q] = (slot ^ dual_swz<XROWB>(row)) * 8;
   }
+  // BNA: the wave's bit dword -- lane l: dword l % 8 of the row of piece (l / 16) * 4 + wave, half (l / 8) % 2; it lands at
+  // B_OFF + wave * 256 + l * 4, i.e. the 32 bytes of (piece q, half h) start at B_OFF + wave * 256 + (2 * q + h) * 32
+  const int b_row = (((lane >> 4) * 4 + wave) << 1) | ((lane >> 3) & 1), b_col = (lane & 7) * 4;
+  float pm[8], pis[8], pa[8], pb[8], pc[8];
+  (void)pm; (void)pis; (void)pa; (void)pb; (void)pc; (void)b_row; (void)b_col;
+  if constexpr (BNA) {
+    const int c0 = y_col[0];                                 // (= y_col[q] for every q: see the kernel's header)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      pm[j] = P.MEAN[c0 + j]; pis[j] = P.INVSTD[c0 + j];
+      pa[j] = P.COEF[c0 + j]; pb[j] = P.COEF[CO + c0 + j]; pc[j] = P.COEF[2 * CO + c0 + j];
+    }
+  }
 // both streams (dY rows, X rows) are read once: non-temporal (-DRIGL_B1_NO_NT: without; in the step conv_bwd 3.601 / 3.598 ->
 // 3.542 / 3.544 ms, 10.409 / 10.392 -> 10.344 / 10.354 ms)
 #if !defined(RIGL_B1_NO_NT) && !defined(RIGL_DMA_BUILTIN)
@@ -113,6 +151,11 @@ __global__ __launch_bounds__(THREADS) void k_bwd1x1(Bwd1x1Args P) {
       const int p_ = p0_ + y_row[q];                                                                     \
       const int off_ = p_ < P.M ? (int)((uint32_t)(p_ * CO + y_col[q]) * 2u) : (int)OOB;                 \
       B1_DMA16(rsrcY, smem + (stage_) * STAGE + (q * 4 + wave) * 1024, off_); \
+      if (BNA) lds_dma16_nt(rsrcZ4, smem + (stage_) * STAGE + Y3_OFF + (q * 4 + wave) * 1024, off_);       \
+    }                                                                                                    \
+    if (BNA) {                                                                                           \
+      const int p_ = p0_ + b_row;                                                                        \
+      lds_dma4(rsrcB4, smem + (stage_) * STAGE + B_OFF + wave * 256, p_ < P.M ? p_ * (CO / 8) + b_col : (int)OOB); \
     }                                                                                                    \
     if (DO_W) {                                                                                          \
       _Pragma("unroll") for (int q = 0; q < XPW; ++q) {                                                  \
@@ -196,6 +239,30 @@ __global__ __launch_bounds__(THREADS) void k_bwd1x1(Bwd1x1Args P) {
       else wait_vmcnt<W_N>();
     } else {
       wait_vmcnt<0>();
+    }
+    if constexpr (BNA) {
+      // dout -> dy3 in place, on the pieces this wave's own DMA instructions wrote (its vmcnt wait above covers them)
+      unsigned char* const Yw = smem + (kt % NST) * STAGE;
+      const int p0 = (kt_begin + kt * kt_step) * PX;
+#pragma unroll
+      for (int q = 0; q < YPW; ++q) {
+        unsigned char* const pd = Yw + (q * 4 + wave) * 1024 + lane * 16;
+        const uint4 d4 = *reinterpret_cast<const uint4*>(pd), x4 = *reinterpret_cast<const uint4*>(pd + Y3_OFF);
+        const uint32_t mb = Yw[B_OFF + wave * 256 + (2 * q + (lane >> 5)) * 32 + (y_col[q] >> 3)];
+        const bool rowok = p0 + y_row[q] < P.M;               // (rows beyond the tensor read zeros: they stay zeros)
+        uint32_t o4[4];
+#pragma unroll
+        for (int dd = 0; dd < 4; ++dd) {
+          const uint32_t dw_ = dword_of(d4, dd), xw_ = dword_of(x4, dd);
+          const float dz0 = (mb >> (2 * dd)) & 1u ? __uint_as_float(dw_ << 16) : 0.f;
+          const float dz1 = (mb >> (2 * dd + 1)) & 1u ? __uint_as_float(dw_ & 0xFFFF0000u) : 0.f;
+          const f32x2 o = {bn_bwd_dx(dz0, __uint_as_float(xw_ << 16), pm[2 * dd], pis[2 * dd], pa[2 * dd], pb[2 * dd], pc[2 * dd]),
+                           bn_bwd_dx(dz1, __uint_as_float(xw_ & 0xFFFF0000u), pm[2 * dd + 1], pis[2 * dd + 1], pa[2 * dd + 1],
+                                     pb[2 * dd + 1], pc[2 * dd + 1])};
+          o4[dd] = rowok ? __builtin_bit_cast(uint32_t, __builtin_convertvector(o, bf16x2)) : 0u;
+        }
+        *reinterpret_cast<uint4*>(pd) = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+      }
     }
     // this wave's dX tile of the previous iteration (ds_write, read by OTHER waves in B1_FLUSH below) must have reached
     // the LDS before the barrier releases them: a raw s_barrier does not wait for LDS writes (round 4: dX wrong in ~1 run
@@ -301,8 +368,9 @@ __global__ __launch_bounds__(THREADS) void k_bwd1x1(Bwd1x1Args P) {
 static inline int bwd1x1_kind(const RiglConvDesc* d) {
   if (d->kh != 1 || d->kw != 1 || d->stride_h != 1 || d->stride_w != 1 || d->pad_top || d->pad_left) return 0;
   if (d->ho != d->h || d->wo != d->w) return 0;            // (a cropped output grid: the generic bodies walk ho x wo)
-  if ((int64_t)d->n * d->h * d->w < 65536) return 0;
-  if (RIGL_TUNE("bwd1x1", 1) == 0) return 0;
+  // ("bwd1x1" = 2: from 8 192 rows on -- more workgroups than K-tiles below 16 384; the default rule keeps the measured sizes)
+  const int knob = RIGL_TUNE("bwd1x1", 1);
+  if (knob == 0 || (int64_t)d->n * d->h * d->w < (knob == 2 ? 8192 : 65536)) return 0;
   if (d->cin == 64 && d->cout == 256) return 1;
   // (256 -> 64 measured level with the fused igemm launch, 109 vs 110 us at batch 128: not instantiated)
   if (d->cin == 64 && d->cout == 64) return 3;
@@ -353,4 +421,28 @@ static bool launch_bwd1x1(const RiglConvDesc* d, const rigl_bf16* x, const rigl_
     case 3: return launch_bwd1x1_t<64, 64>(a, w, st);
     default: return false;
   }
+}
+
+// ---- the BNA kernel: 64 -> 256, weight gradient included, four stages, one workgroup per CU ------------------------------------
+// Knob "bn_bwd_on_load": 1 = the layers the plain kernel takes with 256 output channels (default), 0 = none.
+static bool bwd1x1_bna_ready(const RiglConvDesc* d) {
+  if (!RIGL_TUNE("bn_bwd_on_load", 1) || bwd1x1_kind(d) != 1 || !bwd1x1_ready(d)) return false;
+  constexpr int SMEM = Bwd1x1Smem<64, 256, true, 4, true>::BYTES;
+  static_assert(SMEM <= 160 * 1024, "the ring fits a CU's LDS");
+  static const bool ready = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bwd1x1<64, 256, true, 4, true>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) == hipSuccess;
+  return ready;
+}
+static bool launch_bwd1x1_bna(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dout, const rigl_bf16* w_hwio,
+                              const rigl_bf16* addend, rigl_bf16* dx, float* slab, const rigl_bf16* y3, const uint8_t* bits,
+                              const float* mean, const float* invstd, const float* coef, hipStream_t st) {
+  if (!bwd1x1_bna_ready(d)) return false;
+  Bwd1x1Args a = {};
+  a.X = x; a.DY = dout; a.W = w_hwio; a.ADD = addend; a.DX = dx; a.SLAB = slab;
+  a.M = d->n * d->h * d->w; a.splits = bwd1x1_splits(); a.interleave = RIGL_TUNE("bwd1x1_il", 1);
+  a.x_bytes = (uint32_t)((size_t)a.M * d->cin * 2); a.dy_bytes = (uint32_t)((size_t)a.M * d->cout * 2);
+  a.Y3 = y3; a.BITS = bits; a.MEAN = mean; a.INVSTD = invstd; a.COEF = coef;
+  RIGL_K_LAUNCH((k_bwd1x1<64, 256, true, 4, true>), dim3((unsigned)a.splits), dim3(THREADS),
+                (Bwd1x1Smem<64, 256, true, 4, true>::BYTES), st, a);
+  return true;
 }

@@ -103,4 +103,14 @@ __device__ __forceinline__ uint4 gate_bf16x8(uint4 v, uint4 x) {
   return make_uint4(gate_bf16x2(v.x, x.x), gate_bf16x2(v.y, x.y), gate_bf16x2(v.z, x.z), gate_bf16x2(v.w, x.w));
 }
 
+// ---- the batch norm's backward apply on one element: dx = a * (dz - b - xhat * c), xhat = (x - mean) * invstd, with
+// a = gamma * invstd, b = mean(dz), c = mean(dz * xhat) (k_bwd_finalize's coef[3][C]) and dz the relu-masked output gradient.
+// ONE statement of the arithmetic and its rounding points for bn.hip's k_bwd_apply and for the 1x1 backward that applies it
+// on its dY load (bwd1x1.hpp): the library is built with -ffp-contract=off, so both kernels evaluate exactly these five
+// operations in this order and the products are bit-identical.
+__device__ __forceinline__ float bn_bwd_dx(float dz, float x, float mean, float invstd, float a, float b, float c) {
+  const float xh = (x - mean) * invstd;
+  return a * (dz - b - xh * c);
+}
+
 }  // namespace rigl

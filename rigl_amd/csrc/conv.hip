@@ -2028,7 +2028,7 @@ static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* 
     dgrad_pp = plan_pp<1>(ap).variant != 0;
   }
   // The big-M 1x1 layers: dX and dW in ONE pass over dY (bwd1x1.hpp), one slab per workgroup, then the reduce
-  if (whole && !bn && bwd1x1_kind(d) && bwd1x1_ready(d)) {
+  if (whole && !bn && !addend_bits && bwd1x1_kind(d) && bwd1x1_ready(d)) {
     if (need && (!workspace || workspace_bytes < need))
       return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_bwd: workspace %zu < %zu", workspace_bytes, need);
     ProfFamily prof(PROF_CONV_BWD);
@@ -2056,7 +2056,8 @@ static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* 
       return RIGL_OK;
     }
   }
-  if (addend_bits) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_masked: this layer's kernels take no masked addend (ask rigl_conv2d_bwd_takes_masked_addend)");
+  if (addend_bits && !(whole && rs_masked_use(d)))
+    return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_masked: this layer's kernels take no masked addend (ask rigl_conv2d_bwd_takes_masked_addend)");
   // Layers whose dgrad streams rows (rowstream.hpp): the weight gradient with its stand-alone plan, then the dgrad -- two
   // launches (+ reduce) instead of the shared one
   {
@@ -2066,7 +2067,7 @@ static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* 
       rc = rigl_masked_conv2d_wgrad(d, x, dy, dw, workspace, workspace_bytes, stream);
       if (rc) return rc;
       prof_current_kind() = PROF_CONV_BWD;
-      launch_rs<1>(d, rp, dy, w_hwio, addend, dx, nullptr, st);
+      launch_rs<1>(d, rp, dy, w_hwio, addend, dx, nullptr, st, addend_bits);
       RIGL_CHECK_LAUNCH("rigl_masked_conv2d_bwd");
       return RIGL_OK;
     }
@@ -2207,13 +2208,57 @@ int rigl_masked_conv2d_bwd(const RiglConvDesc* d, const rigl_bf16* x, const rigl
 // rigl_masked_conv2d_bwd whose addend arrives UNMASKED together with a 1-bit-per-element mask (bit set = the addend counts):
 // the gradient of relu(bn3 + shortcut) w.r.t. the shortcut is the block output's gradient where the ReLU was on
 // (resnet_model.py:497-501), so the batch norm's backward need not write that masked copy -- its consumer, the dgrad
-// epilogue of the block's first conv, masks on the fly.  Only the layers of rigl_conv2d_bwd_takes_masked_addend.
+// epilogue of the block's first conv, masks on the fly.  The layers of rigl_conv2d_bwd_takes_masked_addend, and every other layer
+// whose row-streaming dgrad has the masked form (256 <- 64 from 4 096 rows on; the query adds the measured row count).
 int32_t rigl_conv2d_bwd_takes_masked_addend(const RiglConvDesc* d) {
   using namespace rigl;
   using namespace rigl::k1;
   if (!d || check_desc(d, "rigl_conv2d_bwd_takes_masked_addend")) return 0;
-  return bs_use(d) ? 1 : 0;
+  if (bs_use(d)) return 1;
+  // (the order of bwd_impl: a layer the single-pass 1x1 kernel takes never reaches the row-streaming dgrad)
+  if ((bwd1x1_kind(d) && bwd1x1_ready(d)) || !rs_masked_use(d)) return 0;
+  // The row-streaming dgrad: rigl_masked_conv2d_bwd_masked runs wherever the kernel is legal, but a caller that asks here
+  // whether to SKIP writing the masked copy is told yes only from 65 536 rows on (measured at batch 128, 401 408 rows;
+  // below that the graph keeps its former hand-over); knob "rs_masked_addend" = 2: every legal layer.
+  return RIGL_TUNE("rs_masked_addend", 1) == 2 || (int64_t)d->n * d->h * d->w >= 65536 ? 1 : 0;
 }
+// rigl_masked_conv2d_bwd of the conv IN FRONT of a batch norm whose backward apply pass is not run: `dout` is the gradient w.r.t.
+// relu(bn(y) + shortcut), and the kernel forms dy = bf16(a * (dz - b - xhat * c)) on its operand load from dout, y (this conv's
+// forward output), the ReLU bits and mean / invstd / coef (rigl_bn_bwd_reduce).  dX and dW have the bits of rigl_bn_bwd followed
+// by rigl_masked_conv2d_bwd.  Only the layers of rigl_conv2d_bwd_takes_bn_apply.
+int32_t rigl_conv2d_bwd_takes_bn_apply(const RiglConvDesc* d) {
+  using namespace rigl;
+  using namespace rigl::k1;
+  if (!d || check_desc(d, "rigl_conv2d_bwd_takes_bn_apply")) return 0;
+  return bwd1x1_bna_ready(d) ? 1 : 0;
+}
+int rigl_masked_conv2d_bwd_bnapply(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dout, const rigl_bf16* w_hwio,
+                                   const rigl_bf16* addend, float* dw, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
+                                   const rigl_bf16* y, const uint8_t* relu_bits, const float* mean, const float* invstd,
+                                   const float* coef, rigl_stream_t stream) {
+  using namespace rigl;
+  using namespace rigl::k1;
+  int rc = check_desc(d, "rigl_masked_conv2d_bwd_bnapply");
+  if (rc) return rc;
+  if (!x || !dout || !w_hwio || !dw || !dx || !y || !relu_bits || !mean || !invstd || !coef)
+    return fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd_bnapply: NULL tensor");
+  if (!bwd1x1_bna_ready(d))
+    return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_bnapply: this layer's backward does not take the transform (rigl_conv2d_bwd_takes_bn_apply)");
+  const size_t need = rigl_conv2d_workspace_bytes(d, 2);
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_bwd_bnapply: workspace %zu < %zu", workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  prof_set_tag(d);
+  ProfFamily prof(PROF_CONV_BWD);
+  if (!launch_bwd1x1_bna(d, x, dout, w_hwio, addend, dx, static_cast<float*>(workspace), y, relu_bits, mean, invstd, coef, st))
+    return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_bnapply: the kernel did not launch");
+  const int64_t n_out = (int64_t)d->cin * d->cout;
+  ReduceArgs ra = {static_cast<const float*>(workspace), dw, n_out, n_out, bwd1x1_splits()};
+  launch_wgrad_reduce(ra, st);
+  RIGL_CHECK_LAUNCH("rigl_masked_conv2d_bwd_bnapply");
+  return RIGL_OK;
+}
+
 int rigl_masked_conv2d_bwd_masked(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
                                   const rigl_bf16* addend, const uint8_t* addend_bits, float* dw, rigl_bf16* dx,
                                   void* workspace, size_t workspace_bytes, rigl_stream_t stream) {

@@ -50,6 +50,7 @@ struct RsArgs {
   const float* BNP;            // BNL kernels: [2][K] scale, shift of the batch norm in front of this conv
   uint16_t* A2;                // BNL kernels: [M][K] bf16, the activated operand (side output, the backward reads it)
   const float* EPS;            // eval kernels (RS_EPI_BN): [2][N] scale, shift of the frozen batch norm behind this conv
+  const uint8_t* ABITS;        // MODE 3: [M][N / 8] bytes, bit j of byte g = the addend of channel 8 g + j counts
 };
 #ifdef RIGL_RS_TRACE
 #define RS_STAMP(i_) { if (tid == 0 && P.TRACE && (i_) < 64) P.TRACE[blockIdx.x * 64 + (i_)] = __builtin_amdgcn_s_memtime(); }
@@ -64,6 +65,11 @@ __device__ __forceinline__ uint32_t rs_add_bf16x2(uint32_t a, uint32_t b) {
   const f32x2 s = {__uint_as_float(a << 16) + __uint_as_float(b << 16),
                    __uint_as_float(a & 0xFFFF0000u) + __uint_as_float(b & 0xFFFF0000u)};
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(s, bf16x2));
+}
+
+// MODE 3: the two low bits of m -> an all-ones / all-zeros mask per bf16 half (bit 0 = the low half = the even channel)
+__device__ __forceinline__ uint32_t rs_mask_bf16x2(uint32_t m) {
+  return ((0u - (m & 1u)) & 0x0000FFFFu) | ((0u - ((m >> 1) & 1u)) & 0xFFFF0000u);
 }
 
 // BNL kernels: the batch-norm apply + ReLU of bn.hip's k_fwd_apply on one A fragment (8 consecutive reduction channels of one
@@ -101,7 +107,10 @@ struct RsGeom {
 // the plain forward followed by that apply pass.  The residual is a bf16 [M][N] tensor at the output's offsets, requested at the
 // top of the fragment through the ADD resource of MODE 2.  No statistics are summed and, with BNL, no A2 side output is written.
 constexpr int RS_EPI_EVAL = 8, RS_EPI_BN = 1, RS_EPI_RES = 2, RS_EPI_RELU = 4;
-// MODE 0 = forward (statistics always summed, written if STATS is given), 1 = dgrad, 2 = dgrad + addend
+// MODE 0 = forward (statistics always summed, written if STATS is given), 1 = dgrad, 2 = dgrad + addend, 3 = dgrad + an addend
+// that arrives UNMASKED with the 1-bit mask k_fwd_apply leaves (bn.hip): bf16(bf16(acc) + (bit ? addend : 0)).  A lane's 16
+// bytes of an output row are eight consecutive channels = ONE mask byte, at a sixteenth of the output's byte offset; the bytes
+// are requested at the top of the fragment together with the addend (ITERS more registers, no load under a branch).
 // BNL (forward only; VERDICT r5 item 2, "batch-norm apply + ReLU on the operand load"): A is the PRE-batch-norm tensor; every A
 // fragment becomes bf16(max(x * scale[k] + shift[k], 0)) in its ring registers one k-step before its MFMAs (under the previous
 // step's), so the product is conv(relu(bn(x))) with the rounding points of the separate apply pass, which is then not run;
@@ -112,7 +121,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_rowstream(RsArgs P) {
   static_assert(!BNL || MODE == 0, "the on-load transform belongs to the forward");
   static_assert(EPI == 0 || (MODE == 0 && (EPI & RS_EPI_EVAL)), "the eval epilogue belongs to the forward");
   constexpr bool EVAL = EPI != 0, EBN = (EPI & RS_EPI_BN) != 0, ERES = EBN && (EPI & RS_EPI_RES), ERELU = EBN && (EPI & RS_EPI_RELU);
-  constexpr bool DGRAD = MODE != 0, ADDEND = MODE == 2 || ERES, STATS = !DGRAD && !EVAL, A2OUT = BNL && !EVAL;
+  constexpr bool MADD = MODE == 3;
+  constexpr bool DGRAD = MODE != 0, ADDEND = MODE == 2 || MADD || ERES, STATS = !DGRAD && !EVAL, A2OUT = BNL && !EVAL;
   using G = RsGeom<KC, TN>;
   constexpr int NS = G::NS, RB = G::RB, CPR = G::CPR, SROW = G::SROW;
   constexpr int CHR = 4 * TN, RPI = 64 / CHR, ITERS = 32 / RPI;    // 16-byte chunks per staged row, rows per store iteration
@@ -129,6 +139,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rowstream(RsArgs P) {
   const __amdgpu_buffer_rsrc_t rsrcA = make_rsrc(P.A, P.a_bytes), rsrcB = make_rsrc(P.B, P.b_bytes);
   const __amdgpu_buffer_rsrc_t rsrcD = make_rsrc(ADDEND ? P.ADD : P.A, ADDEND ? P.c_bytes : 0u);
   const __amdgpu_buffer_rsrc_t rsrcC = make_rsrc(P.C, P.c_bytes);
+  const __amdgpu_buffer_rsrc_t rsrcM = make_rsrc(MADD ? (const void*)P.ABITS : (const void*)P.A, MADD ? P.c_bytes >> 4 : 0u);
 
   float* const prm = reinterpret_cast<float*>(smem_rs + G::SMEM);           // BNL: [2][K]
   const __amdgpu_buffer_rsrc_t rsrcA2 = make_rsrc(A2OUT ? P.A2 : P.C, A2OUT ? P.a_bytes : 0u);
@@ -210,6 +221,12 @@ __global__ __launch_bounds__(RS_THREADS) void k_rowstream(RsArgs P) {
       if (ADDEND) {
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) addv[it] = buf_load16(rsrcD, coff[it]);   // (non-temporal measured level: profiles/r6)
+      }
+      uint32_t mbit[MADD ? ITERS : 1];
+      if constexpr (MADD) {
+        // (an out-of-range coff is >= 2^31: its sixteenth is beyond the mask's < 2^26 bytes too, and reads zero)
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) mbit[it] = __builtin_amdgcn_raw_buffer_load_b8(rsrcM, (int)(coff[it] >> 4), 0, 0);
       }
       f32x16 acc[TN];
 #pragma unroll
@@ -315,7 +332,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_rowstream(RsArgs P) {
         } else if (ADDEND) {
 #pragma unroll
           for (int i4 = 0; i4 < 4; ++i4) {
-            const uint4 q4 = addv[g0 + i4];
+            uint4 q4 = addv[g0 + i4];
+            if constexpr (MADD) {
+              const uint32_t mb = mbit[g0 + i4];
+              q4.x &= rs_mask_bf16x2(mb); q4.y &= rs_mask_bf16x2(mb >> 2); q4.z &= rs_mask_bf16x2(mb >> 4); q4.w &= rs_mask_bf16x2(mb >> 6);
+            }
             v[i4].x = rs_add_bf16x2(v[i4].x, q4.x); v[i4].y = rs_add_bf16x2(v[i4].y, q4.y);
             v[i4].z = rs_add_bf16x2(v[i4].z, q4.z); v[i4].w = rs_add_bf16x2(v[i4].w, q4.w);
           }
@@ -469,20 +490,33 @@ static bool rs_use(const RiglConvDesc* d, RsPlan* out = nullptr) {
   if (ready && out) *out = p;
   return ready;
 }
+// The dgrad whose addend arrives unmasked with its 1-bit mask (MODE 3): instantiated for the 256 <- 64 layers (K = 64, TN = 4), the
+// only ones whose one-call backward runs the row-streaming dgrad by default; knob "rs_masked_addend": 0 = none (the caller then
+// hands over a masked copy, as before), 1 = rigl_conv2d_bwd_takes_masked_addend says yes from 65 536 rows on, 2 = for every such layer.
+static bool rs_masked_use(const RiglConvDesc* d, RsPlan* out = nullptr) {
+  RsPlan p;
+  if (!RIGL_TUNE("rs_masked_addend", 1) || !rs_use<1>(d, &p)) return false;
+  if (p.kc != 1 || p.tn != 4) return false;
+  if (!rs_ready_i<1, 4, 3>()) return false;
+  if (out) *out = p;
+  return true;
+}
 template <int MODE>
 static void launch_rs(const RiglConvDesc* d, const RsPlan& p, const rigl_bf16* a_act, const rigl_bf16* b_w, const rigl_bf16* addend,
-                      rigl_bf16* c_out, float* stats, hipStream_t st) {
+                      rigl_bf16* c_out, float* stats, hipStream_t st, const uint8_t* addend_bits = nullptr) {
   RsArgs a = {};
 #ifdef RIGL_RS_TRACE
   { const char* e = getenv("RIGL_RS_TRACE_PTR"); a.TRACE = e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0)) : nullptr; }
 #endif
   const int k = MODE == 0 ? d->cin : d->cout, n = MODE == 0 ? d->cout : d->cin;
-  a.A = a_act; a.B = b_w; a.C = c_out; a.ADD = addend; a.STATS = stats;
+  a.A = a_act; a.B = b_w; a.C = c_out; a.ADD = addend; a.STATS = stats; a.ABITS = addend_bits;
   a.M = d->n * d->h * d->w; a.N = n; a.F = p.F; a.nfrag = p.nfrag; a.slices = p.slices; a.gprime = p.gprime;
   a.a_bytes = (uint32_t)((size_t)a.M * k * 2); a.b_bytes = (uint32_t)((size_t)n * k * 2); a.c_bytes = (uint32_t)((size_t)a.M * n * 2);
   const dim3 grid((unsigned)(p.slices * p.gprime)), blk(RS_THREADS);
 #define RS_LAUNCH(KC_, TN_, DG_) RIGL_K_LAUNCH((k_rowstream<KC_, TN_, DG_>), grid, blk, (unsigned)(RsGeom<KC_, TN_>::SMEM), st, a);
-  if (MODE == 0) { RS_DISPATCH(p, 0, RS_LAUNCH) } else if (addend) { RS_DISPATCH(p, 2, RS_LAUNCH) } else { RS_DISPATCH(p, 1, RS_LAUNCH) }
+  if (MODE == 0) { RS_DISPATCH(p, 0, RS_LAUNCH) }
+  else if (addend && addend_bits) { RS_LAUNCH(1, 4, 3) }        // (rs_masked_use said yes: K = 64, TN = 4)
+  else if (addend) { RS_DISPATCH(p, 2, RS_LAUNCH) } else { RS_DISPATCH(p, 1, RS_LAUNCH) }
 #undef RS_LAUNCH
 }
 

@@ -627,8 +627,49 @@ LAZY_ADDEND_BITS = {}
 
 
 def conv_bwd_takes_masked_addend(d):
-  """Does this layer's one-call backward take its addend unmasked + a 1-bit mask (rigl_masked_conv2d_bwd_masked)?"""
+  """Should the producer of this layer's addend hand it over unmasked + a 1-bit mask (rigl_masked_conv2d_bwd_masked) instead
+  of writing the masked copy?  (rigl_conv2d_bwd_takes_masked_addend: the layers whose default selection has the masked form.)"""
   return bool(_plan_cached(d, 'masked_addend', lambda: int(_lib.load().rigl_conv2d_bwd_takes_masked_addend(C.byref(d)))))
+
+
+def conv_bwd_takes_bn_apply(d):
+  """Does this layer's one-call backward apply the backward of the batch norm BEHIND it on its dY load
+  (rigl_masked_conv2d_bwd_bnapply)?  Knob "bn_bwd_on_load" (RIGL_BN_BWD_ON_LOAD) 0 says no for every layer."""
+  if not (mfma_supported(d) and mfma_dgrad_supported(d)):
+    return False
+  return bool(_plan_cached(d, 'bwd_bn_apply', lambda: int(_lib.load().rigl_conv2d_bwd_takes_bn_apply(C.byref(d)))))
+
+
+def conv_bwd_bnapply(d, x, dout, w_hwio, dw, y, relu_bits, saved, coef, addend=None, on_dw_ready=None, dx=None):
+  """conv_bwd of the conv in front of a batch norm whose backward apply pass was not run (bn_bwd_reduce): ``dout`` is the
+  gradient w.r.t. relu(bn(y) + shortcut), ``y`` this conv's forward output, ``relu_bits`` / ``saved`` the batch norm's forward
+  products, ``coef`` bn_bwd_reduce's.  dW into ``dw``; returns dX (+ ``addend``) -- the bits of bn_bwd followed by conv_bwd."""
+  if not conv_bwd_takes_bn_apply(d):
+    raise ValueError('this layer\'s backward does not take the batch-norm apply (conv_bwd_takes_bn_apply)')
+  for t, nm in ((x, 'x'), (dout, 'dout'), (w_hwio, 'w_hwio'), (y, 'y')):
+    _req(t, torch.bfloat16, nm)
+  _req(addend, torch.bfloat16, 'addend', allow_none=True)
+  _req(dw, torch.float32, 'dw'); _req(saved, torch.float32, 'saved'); _req(coef, torch.float32, 'coef')
+  _req(relu_bits, torch.uint8, 'relu_bits')
+  n_out = d.n * d.ho * d.wo * d.cout
+  if dout.numel() != n_out or y.numel() != n_out or relu_bits.numel() * 8 != n_out:
+    raise ValueError('dout and y must have the shape of the conv output and relu_bits one bit per element of it')
+  if saved.numel() != 4 * d.cout or coef.numel() != 3 * d.cout:
+    raise ValueError('saved must be [4, Cout] and coef [3, Cout]')
+  if addend is not None and addend.numel() != d.n * d.h * d.w * d.cin:
+    raise ValueError('addend must have the shape of dx')
+  lib = _lib.load()
+  _count_macs('wgrad_macs', d)
+  _count_macs('dgrad_macs', d)
+  need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
+  ws = workspace(need, x.device, 'wg') if need else None
+  dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dout.device, 'dx')
+  check(lib.rigl_masked_conv2d_bwd_bnapply(C.byref(d), _ptr(x), _ptr(dout), _ptr(w_hwio), _ptr(addend), _ptr(dw), _ptr(dx), _ptr(ws),
+                                           ws.numel() if ws is not None else 0, _ptr(y), _ptr(relu_bits), _ptr(saved[0]),
+                                           _ptr(saved[1]), _ptr(coef), _stream()))
+  if on_dw_ready is not None:
+    on_dw_ready()
+  return dx
 
 
 def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, bn_fuse=None, addend_sub=None,
@@ -647,8 +688,9 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
     addend_sub = None
   if addend_bits is not None:
     # ``addend_bits`` (uint8, one bit per element of ``addend``): the addend counts only where its bit is set
-    if addend is None or not need_dx or bn_fuse is not None or addend_sub is not None or not conv_bwd_takes_masked_addend(d):
-      raise ValueError('addend_bits needs an addend, dX and a layer whose backward takes a masked addend')
+    # (a layer whose kernels have no masked form is refused by the library: RiglError, RIGL_EUNSUPPORTED)
+    if addend is None or not need_dx or bn_fuse is not None or addend_sub is not None:
+      raise ValueError('addend_bits needs an addend and dX, and combines with neither bn_fuse nor addend_sub')
     _req(x, torch.bfloat16, 'x'); _req(dy, torch.bfloat16, 'dy'); _req(dw, torch.float32, 'dw')
     _req(addend, torch.bfloat16, 'addend'); _req(addend_bits, torch.uint8, 'addend_bits'); _req(w_hwio, torch.bfloat16, 'w_hwio')
     if addend.numel() != d.n * d.h * d.w * d.cin or addend_bits.numel() * 8 != addend.numel():
@@ -977,6 +1019,25 @@ def bn_bwd(x, y, dy, gamma, saved, relu, dgamma, dbeta, want_dres=False,
                               partials.shape[0] if partials is not None else 0, _ptr(ws), ws.numel(),
                               _stream()))
   return dx, dres
+
+
+def bn_bwd_reduce(x, dy, gamma, saved, relu, relu_bits, dgamma, dbeta):
+  """bn_bwd without its apply pass (rigl_bn_bwd_reduce): dgamma / dbeta (fp32 [C]) are overwritten; returns coef, fp32 [3, C]
+  (a = gamma * invstd, b = mean dz, c = mean dz * xhat), for conv_bwd_bnapply of the conv that produced ``x``."""
+  _req(x, torch.bfloat16, 'x')
+  _req(dy, torch.bfloat16, 'dy')
+  _req(relu_bits, torch.uint8, 'relu_bits', allow_none=not relu)
+  c = x.shape[-1]
+  m = x.numel() // c
+  if dy.numel() != x.numel() or (relu and relu_bits.numel() * 8 != x.numel()):
+    raise ValueError('dy must have the shape of x and relu_bits one bit per element of it')
+  lib = _lib.load()
+  coef = torch.empty((3, c), dtype=torch.float32, device=x.device)
+  ws = workspace(lib.rigl_bn_workspace_bytes(m, c), x.device)
+  check(lib.rigl_bn_bwd_reduce(m, c, _ptr(x), _ptr(relu_bits) if relu else None, _ptr(dy), _ptr(gamma), _ptr(saved[0]),
+                               _ptr(saved[1]), int(bool(relu)), _ptr(dgamma), _ptr(dbeta), _ptr(coef), _ptr(ws), ws.numel(),
+                               _stream()))
+  return coef
 
 
 # ----------------------------------------------------------------------------

@@ -70,6 +70,36 @@ def _bn_fuse_publish(holder, req, dx):
     holder.partials, holder.dx_ptr = req['partials'], dx.data_ptr()
 
 
+class BnApplyHolder:
+  """Shared by the autograd nodes of a conv whose backward applies the backward of the batch norm BEHIND it on its dY load
+  (ops.conv_bwd_takes_bn_apply) and of that batch norm (workloads.nn._FusedBNFn).  Forward: the conv leaves it on its output
+  (attribute ``bn_apply``); the batch norm sets ``armed`` where it will skip its apply pass.  Backward: the batch norm runs
+  ops.bn_bwd_reduce, fills dout / y / bits / saved / coef and returns dout itself; the conv, one node later, takes them."""
+  __slots__ = ('armed', 'dout', 'y', 'bits', 'saved', 'coef')
+
+  def __init__(self):
+    self.armed = False
+    self.dout = self.y = self.bits = self.saved = self.coef = None
+
+  def fill(self, dout, y, bits, saved, coef):
+    self.dout, self.y, self.bits, self.saved, self.coef = dout, y, bits, saved, coef
+
+  def take(self, dy):
+    """The batch norm's products for the conv's backward, or None for the plain backward; raises where the two nodes
+    disagree (the gradient that arrived is then not what this conv's kernels would be run on)."""
+    filled = self.dout is not None
+    if self.armed != filled:
+      raise RuntimeError('bn_bwd_on_load: the batch norm %s its apply pass but the forward had decided otherwise'
+                         % ('skipped' if filled else 'ran'))
+    if not filled:
+      return None
+    if dy is not self.dout and (dy.data_ptr() != self.dout.data_ptr() or dy.shape != self.dout.shape or not dy.is_contiguous()):
+      raise RuntimeError('bn_bwd_on_load: the gradient that reached the conv is not the one the batch norm handed over')
+    got = (self.dout, self.y, self.bits, self.saved, self.coef)
+    self.dout = self.y = self.bits = self.saved = self.coef = None
+    return got
+
+
 def _mask_bits(lv):
   """The layer's mask bitmap for the fp32 kernels (they read the master weights and apply the mask on the fly)."""
   return lv.mask.bits if lv.mask is not None else None
@@ -123,6 +153,14 @@ class _MaskedConvFn(torch.autograd.Function):
     if x.dtype == torch.float32:
       dx = ops.conv_bwd_f32(d, x, dy, lv.weights.data.view(-1), _mask_bits(lv), lv.weights.grad.view(-1),
                             need_dx=ctx.need_dx, on_dw_ready=ready)
+      return dx, None, None, None, None, None, None
+    # (MaskedConv2d.__call__ leaves the holder on the node once the forward has run: it is not an input of the function)
+    apply_holder = getattr(ctx, 'apply_holder', None)
+    got = apply_holder.take(dy) if apply_holder is not None else None
+    if got is not None:
+      # dy is the gradient w.r.t. the OUTPUT of the batch norm behind this conv: its apply pass runs on this backward's dY load
+      dout, y, bits, saved, coef = got
+      dx = ops.conv_bwd_bnapply(d, x, dout, lv.hwio, lv.weights.grad.view(-1), y, bits, saved, coef, on_dw_ready=ready)
       return dx, None, None, None, None, None, None
     req = _bn_fuse_request(ctx.bn_holder, ctx.need_dx)
     dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=ctx.need_dx, on_dw_ready=ready, bn_fuse=req)
@@ -365,11 +403,17 @@ class MaskedConv2d(_Layer):
       raise RuntimeError('a deferred batch-norm output must reach its consumer conv as it was returned')
     if not x.requires_grad:
       x = x.detach().requires_grad_(True)  # keep the node so wgrad runs
+    # the batch norm behind this conv may leave its backward apply pass to this conv's backward (workloads.nn.BatchNorm)
+    apply_holder = BnApplyHolder() if (need_dx and x.dtype == torch.bfloat16 and x.is_cuda and ops.conv_bwd_takes_bn_apply(d)) else None
     if not bn_stats:
-      return _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, False, holder, pending)
-    y, part = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, True, holder, pending)
-    if part.numel():
-      y.bn_partials = part
+      y = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, False, holder, pending)
+    else:
+      y, part = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, True, holder, pending)
+      if part.numel():
+        y.bn_partials = part
+    if apply_holder is not None and y.grad_fn is not None:
+      y.grad_fn.apply_holder = apply_holder          # the conv's autograd node (its ctx) ...
+      y.bn_apply = apply_holder                      # ... and the batch norm that reads y share it
     return y
 
   def conv_relu(self, x, gate_input=True):

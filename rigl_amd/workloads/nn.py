@@ -64,13 +64,22 @@ class _FusedBNFn(torch.autograd.Function):
   the conv kernels' dW; autograd only routes dx (and the residual's grad)."""
 
   @staticmethod
-  def forward(ctx, x, residual, bn, relu, partials=None, holder=None, lazy_res_grad=False, defer=False):
+  def forward(ctx, x, residual, bn, relu, partials=None, holder=None, lazy_res_grad=False, defer=False, apply_holder=None):
     from rigl_amd import ops  # pylint: disable=import-outside-toplevel
+    x_in = x
     x = x.contiguous()
     res = residual.contiguous() if residual is not None else None
     ctx.bn, ctx.relu, ctx.has_res = bn, relu, res is not None
     ctx.holder = holder
     ctx.lazy_res_grad = bool(lazy_res_grad) and relu and res is not None
+    # the conv that produced x applies this batch norm's backward on its own dY load (pruning_layers.BnApplyHolder): only where
+    # the gradient of relu(bn + residual) leaves this node as it came in -- the residual's consumer masks on the fly
+    # (lazy_res_grad) -- so that nothing of the apply pass is left to write; decided here, and the conv's backward checks it
+    ctx.apply_holder = None
+    if (apply_holder is not None and ctx.lazy_res_grad and not defer and x is x_in and ctx.needs_input_grad[0]
+        and ctx.needs_input_grad[1]):
+      ctx.apply_holder = apply_holder
+      apply_holder.armed = True
     if defer:
       # statistics only: the consumer conv applies the batch norm + ReLU on its operand load and FILLS y as a side output
       # (MaskedConv2d picks x and saved up from the holder: y.bn_pending)
@@ -111,18 +120,24 @@ class _FusedBNFn(torch.autograd.Function):
       if h.partials is not None and h.dx_ptr == dy.data_ptr():
         part = h.partials
       h.partials = h.x = h.saved = h.bits = None
+    if ctx.apply_holder is not None:
+      # reductions + finalize only; the apply pass runs on the dY load of the conv that produced x, which receives dy itself
+      coef = ops.bn_bwd_reduce(x, dy, bn.gamma.data, saved, True, bits, bn.gamma.grad, bn.beta.grad)
+      ctx.apply_holder.fill(dy, x, bits, saved, coef)
+      ops.LAZY_ADDEND_BITS[dy.data_ptr()] = (bits, dy)
+      return dy, dy, None, None, None, None, None, None, None
     if ctx.lazy_res_grad and bits is not None and ctx.needs_input_grad[1]:
       # the residual's consumer (the block's first conv, pruning_layers._MaskedConvForkFn) masks on the fly: its gradient is
       # dy where the ReLU was on, so dy itself travels with the ReLU bits and the masked copy is never written
       dx, _ = ops.bn_bwd(x, None, dy, bn.gamma.data, saved, ctx.relu, bn.gamma.grad, bn.beta.grad, want_dres=False,
                          relu_bits=bits, partials=part)
       ops.LAZY_ADDEND_BITS[dy.data_ptr()] = (bits, dy)
-      return dx, dy, None, None, None, None, None, None
+      return dx, dy, None, None, None, None, None, None, None
     dx, dres = ops.bn_bwd(x, None, dy, bn.gamma.data, saved, ctx.relu,
                           bn.gamma.grad, bn.beta.grad,
                           want_dres=ctx.has_res and ctx.needs_input_grad[1],
                           relu_bits=bits, partials=part)
-    return dx, dres, None, None, None, None, None, None
+    return dx, dres, None, None, None, None, None, None, None
 
 
 class _BnAddBnFn(torch.autograd.Function):
@@ -204,7 +219,8 @@ class BatchNorm:
         x = x.detach().requires_grad_(True)
       holder = _BnBwdHolder(relu)
       defer = bool(_BN_ON_LOAD and consumer is not None and relu and residual is None and consumer.takes_bn_input(x))
-      y = _FusedBNFn.apply(x, residual, self, relu, partials, holder, lazy_res_grad and _LAZY_RES_GRAD, defer)
+      apply_holder = getattr(x, 'bn_apply', None)   # left by the producing conv: its backward can take this one's apply pass
+      y = _FusedBNFn.apply(x, residual, self, relu, partials, holder, lazy_res_grad and _LAZY_RES_GRAD, defer, apply_holder)
       y.bn_ctx = holder                            # a masked conv that is this tensor's only consumer picks it up
       if defer:
         y.bn_pending = holder
