@@ -98,6 +98,34 @@ def mask_unpack(bits, shape):
 # ----------------------------------------------------------------------------
 # K2
 # ----------------------------------------------------------------------------
+_K2_OPTIONAL = ('momentum', 'dense_grad', 'drop_noise', 'score_drop', 'score_grow', 'grow_values')
+
+
+def _prune_regrow_layer(slot, l, where=''):
+  """Checks one prune / regrow layer dict and fills its PruneRegrowLayer ``slot``; returns (n, device, momentum2 or None)."""
+  w, m2 = l.get('w'), l.get('momentum2')
+  ref = w if w is not None else l['score_drop']
+  n = ref.numel()
+  for key in ('w', 'momentum2') + _K2_OPTIONAL:
+    t = l.get(key)
+    _req(t, torch.float32, key, allow_none=True)
+    if t is not None and t.numel() != n:
+      raise ValueError('%s%s has %d elements, expected %d' % (where, key, t.numel(), n))
+    if key != 'momentum2':
+      setattr(slot, key, t.data_ptr() if t is not None else None)
+  _req(l['mask_bits'], torch.int32, 'mask_bits')
+  if l['mask_bits'].numel() < n_mask_words(n):
+    raise ValueError('%smask_bits too small' % where)
+  slot.n = n
+  slot.mask_bits = l['mask_bits'].data_ptr()
+  return n, ref.device, m2
+
+
+def _prune_regrow_params(drop_fraction, grow_init_mode, grow_init_div, momentum_reset_mode, initial_acc_scale, reinit_when_same):
+  return PruneRegrowParams(float(drop_fraction), int(grow_init_mode), float(grow_init_div), int(momentum_reset_mode),
+                           float(initial_acc_scale), int(bool(reinit_when_same)))
+
+
 def prune_regrow(layers, drop_fraction, grow_init_mode=_lib.GROW_ZEROS,
                  grow_init_div=1.0, momentum_reset_mode=_lib.MOMRESET_GRAD,
                  initial_acc_scale=0.0, reinit_when_same=False):
@@ -118,37 +146,11 @@ def prune_regrow(layers, drop_fraction, grow_init_mode=_lib.GROW_ZEROS,
   arr = (PruneRegrowLayer * nl)()
   ns = (C.c_int64 * nl)()
   mom2 = (C.c_void_p * nl)()
-  dev = None
   for i, l in enumerate(layers):
-    w = l.get('w')
-    ref = w if w is not None else l['score_drop']
-    n = ref.numel()
-    dev = ref.device
-    for key in ('w', 'momentum', 'momentum2', 'dense_grad', 'drop_noise', 'score_drop',
-                'score_grow', 'grow_values'):
-      t = l.get(key)
-      _req(t, torch.float32, key, allow_none=True)
-      if t is not None and t.numel() != n:
-        raise ValueError('layer %d: %s has %d elements, expected %d' %
-                         (i, key, t.numel(), n))
-    _req(l['mask_bits'], torch.int32, 'mask_bits')
-    if l['mask_bits'].numel() < n_mask_words(n):
-      raise ValueError('layer %d: mask_bits too small' % i)
-    arr[i].n = n
-    arr[i].w = w.data_ptr() if w is not None else None
-    for key in ('momentum', 'dense_grad', 'drop_noise', 'score_drop',
-                'score_grow', 'grow_values'):
-      t = l.get(key)
-      setattr(arr[i], key, t.data_ptr() if t is not None else None)
-    arr[i].mask_bits = l['mask_bits'].data_ptr()
-    m2 = l.get('momentum2')
+    ns[i], dev, m2 = _prune_regrow_layer(arr[i], l, 'layer %d: ' % i)
     mom2[i] = m2.data_ptr() if m2 is not None else None
-    ns[i] = n
-  prm = PruneRegrowParams(float(drop_fraction), int(grow_init_mode),
-                          float(grow_init_div), int(momentum_reset_mode),
-                          float(initial_acc_scale), int(bool(reinit_when_same)))
-  need = lib.rigl_prune_regrow_workspace_bytes(ns, nl)
-  ws = workspace(need, dev)
+  prm = _prune_regrow_params(drop_fraction, grow_init_mode, grow_init_div, momentum_reset_mode, initial_acc_scale, reinit_when_same)
+  ws = workspace(lib.rigl_prune_regrow_workspace_bytes(ns, nl), dev)
   counts = torch.zeros((nl, _lib.COUNTS_PER_LAYER), dtype=torch.int32,
                        device=dev)
   if any(l.get('momentum2') is not None for l in layers):
@@ -168,24 +170,9 @@ def prune_regrow_selections(layer, drop_fraction, grow_init_mode=_lib.GROW_ZEROS
   tensor's indices in tf.nn.top_k order of the drop / lifted grow score; the first counts[2] (n_keep) resp. counts[1]
   (n_prune) entries are the selected ones)."""
   lib = _lib.load()
-  w = layer.get('w')
-  ref = w if w is not None else layer['score_drop']
-  n, dev = ref.numel(), ref.device
   arr = PruneRegrowLayer()
-  arr.n = n
-  arr.w = w.data_ptr() if w is not None else None
-  for key in ('momentum', 'dense_grad', 'drop_noise', 'score_drop', 'score_grow', 'grow_values'):
-    t = layer.get(key)
-    _req(t, torch.float32, key, allow_none=True)
-    setattr(arr, key, t.data_ptr() if t is not None else None)
-  _req(layer['mask_bits'], torch.int32, 'mask_bits')
-  arr.mask_bits = layer['mask_bits'].data_ptr()
-  m2 = layer.get('momentum2')
-  _req(m2, torch.float32, 'momentum2', allow_none=True)
-  if m2 is not None and m2.numel() != n:
-    raise ValueError('momentum2 has %d elements, expected %d' % (m2.numel(), n))
-  prm = PruneRegrowParams(float(drop_fraction), int(grow_init_mode), float(grow_init_div), int(momentum_reset_mode),
-                          float(initial_acc_scale), int(bool(reinit_when_same)))
+  n, dev, m2 = _prune_regrow_layer(arr, layer)
+  prm = _prune_regrow_params(drop_fraction, grow_init_mode, grow_init_div, momentum_reset_mode, initial_acc_scale, reinit_when_same)
   words = n_mask_words(n)
   out = dict(counts=torch.zeros(_lib.COUNTS_PER_LAYER, dtype=torch.int32, device=dev),
              mask1_bits=torch.zeros(words, dtype=torch.int32, device=dev),
@@ -432,10 +419,7 @@ def conv_fwd(d, x, w_ohwi, y=None, force_ref=False, stats=False, *, scale_shift=
   _req(x, torch.bfloat16, 'x')
   _req(w_ohwi, torch.bfloat16, 'w_ohwi')
   _count_macs('fwd_macs', d)
-  if y is None:
-    y = torch.empty((d.n, d.ho, d.wo, d.cout), dtype=torch.bfloat16,
-                    device=x.device)
-  _req(y, torch.bfloat16, 'y')
+  y = _out(y, (d.n, d.ho, d.wo, d.cout), torch.bfloat16, x.device, 'y')
   lib = _lib.load()
   if force_ref or not mfma_supported(d):
     check(lib.rigl_conv2d_fwd_ref(C.byref(d), _ptr(x), _ptr(w_ohwi), _ptr(y),
@@ -507,9 +491,7 @@ def conv_fwd_bnrelu(d, x_pre, saved, w_ohwi, a_out, y=None, stats=False, *, scal
   if saved.numel() != 4 * d.cin or a_out.numel() != x_pre.numel() or x_pre.numel() != d.n * d.h * d.w * d.cin:
     raise ValueError('saved must be [4, Cin]; x_pre and a_out [n, h, w, Cin]')
   _count_macs('fwd_macs', d)
-  if y is None:
-    y = torch.empty((d.n, d.ho, d.wo, d.cout), dtype=torch.bfloat16, device=x_pre.device)
-  _req(y, torch.bfloat16, 'y')
+  y = _out(y, (d.n, d.ho, d.wo, d.cout), torch.bfloat16, x_pre.device, 'y')
   lib = _lib.load()
   if stats:
     parts = _plan_cached(d, 'stats_parts', lambda: lib.rigl_conv2d_stats_parts(C.byref(d)))
@@ -546,9 +528,7 @@ def _conv_fwd_infer(d, x, in_ss, w_ohwi, ss, residual, relu, y):
   _req(residual, torch.bfloat16, 'residual', allow_none=True)
   if residual is not None and residual.numel() != d.n * d.ho * d.wo * d.cout:
     raise ValueError('residual must have the shape of the output')
-  if y is None:
-    y = torch.empty((d.n, d.ho, d.wo, d.cout), dtype=torch.bfloat16, device=x.device)
-  _req(y, torch.bfloat16, 'y')
+  y = _out(y, (d.n, d.ho, d.wo, d.cout), torch.bfloat16, x.device, 'y')
   if conv_fwd_takes_bn_epilogue(d, in_ss is not None, residual is not None):
     _count_macs('fwd_macs', d)
     check(_lib.load().rigl_masked_conv2d_fwd_bn_infer(
@@ -570,10 +550,7 @@ def conv_dgrad(d, dy, w_hwio, dx=None, force_ref=False, addend=None):
   _count_macs('dgrad_macs', d)
   _req(dy, torch.bfloat16, 'dy')
   _req(w_hwio, torch.bfloat16, 'w_hwio')
-  if dx is None:
-    dx = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16,
-                     device=dy.device)
-  _req(dx, torch.bfloat16, 'dx')
+  dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dy.device, 'dx')
   if addend is not None:
     _req(addend, torch.bfloat16, 'addend')
     if addend.numel() != dx.numel():
@@ -596,16 +573,13 @@ def conv_wgrad(d, x, dy, dw=None, force_ref=False):
   _count_macs('wgrad_macs', d)
   _req(x, torch.bfloat16, 'x')
   _req(dy, torch.bfloat16, 'dy')
-  if dw is None:
-    dw = torch.empty(d.kh * d.kw * d.cin * d.cout, dtype=torch.float32,
-                     device=x.device)
-  _req(dw, torch.float32, 'dw')
+  dw = _out(dw, (d.kh * d.kw * d.cin * d.cout,), torch.float32, x.device, 'dw')
   lib = _lib.load()
   if force_ref or not mfma_supported(d):
     check(lib.rigl_conv2d_wgrad_ref(C.byref(d), _ptr(x), _ptr(dy), _ptr(dw),
                                     _stream()))
     return dw
-  need = lib.rigl_conv2d_workspace_bytes(C.byref(d), 2)
+  need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
   ws = workspace(need, x.device) if need else None
   check(lib.rigl_masked_conv2d_wgrad(C.byref(d), _ptr(x), _ptr(dy), _ptr(dw),
                                      _ptr(ws),
@@ -619,11 +593,6 @@ def dgrad_stats_parts(d):
   (0: the layer's dgrad has no such epilogue)."""
   v = _plan_cached(d, 'dgrad_parts', lambda: int(_lib.load().rigl_conv2d_dgrad_stats_parts(C.byref(d))))
   return v
-
-
-# A shortcut gradient handed over UNMASKED: data_ptr of the gradient tensor -> the 1-bit ReLU mask it still has to pass
-# (left by workloads.nn._FusedBNFn.backward, taken by pruning_layers._MaskedConvForkFn.backward one autograd node later).
-LAZY_ADDEND_BITS = {}
 
 
 def conv_bwd_takes_masked_addend(d):
@@ -640,16 +609,44 @@ def conv_bwd_takes_bn_apply(d):
   return bool(_plan_cached(d, 'bwd_bn_apply', lambda: int(_lib.load().rigl_conv2d_bwd_takes_bn_apply(C.byref(d)))))
 
 
+def _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, launch, need_dx=True, dx_shape=None, dgrad_desc=None, f32=False):
+  """The one host transition every one-call conv backward shares: operand checks, the wgrad / dgrad MAC counts, the cached
+  weight-gradient workspace, dX (the caller's, checked, or a fresh one; None without ``need_dx``), ``launch(lib, dx pointer,
+  workspace pointer, workspace bytes)`` -- the form's own C entry point -- and ``on_dw_ready`` once dW's last kernel is enqueued.
+  ``dx_shape`` / ``dgrad_desc``: where dX is not [n, h, w, cin] of ``d``.  ``f32``: the fp32 twin's dtypes and workspace."""
+  act = torch.float32 if f32 else torch.bfloat16
+  _req(x, act, 'x')
+  _req(dy, act, 'dy')
+  _req(dw, torch.float32, 'dw')
+  lib = _lib.load()
+  _count_macs('wgrad_macs', d)
+  if f32:
+    need = _plan_cached(d, 'ws_wgrad_f32', lambda: lib.rigl_conv2d_wgrad_f32_workspace_bytes(C.byref(d)))
+  else:
+    need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
+  ws = workspace(need, x.device, 'wg32' if f32 else 'wg') if need else None
+  if need_dx:
+    _req(w_hwio, act, 'w_hwio')
+    _count_macs('dgrad_macs', dgrad_desc if dgrad_desc is not None else d)
+    dx = _out(dx, dx_shape or (d.n, d.h, d.w, d.cin), act, dy.device, 'dx')
+  else:
+    dx = None
+  check(launch(lib, _ptr(dx), _ptr(ws), ws.numel() if ws is not None else 0))
+  if on_dw_ready is not None:
+    on_dw_ready()
+  return dx
+
+
 def conv_bwd_bnapply(d, x, dout, w_hwio, dw, y, relu_bits, saved, coef, addend=None, on_dw_ready=None, dx=None):
   """conv_bwd of the conv in front of a batch norm whose backward apply pass was not run (bn_bwd_reduce): ``dout`` is the
   gradient w.r.t. relu(bn(y) + shortcut), ``y`` this conv's forward output, ``relu_bits`` / ``saved`` the batch norm's forward
   products, ``coef`` bn_bwd_reduce's.  dW into ``dw``; returns dX (+ ``addend``) -- the bits of bn_bwd followed by conv_bwd."""
   if not conv_bwd_takes_bn_apply(d):
     raise ValueError('this layer\'s backward does not take the batch-norm apply (conv_bwd_takes_bn_apply)')
-  for t, nm in ((x, 'x'), (dout, 'dout'), (w_hwio, 'w_hwio'), (y, 'y')):
-    _req(t, torch.bfloat16, nm)
+  _req(dout, torch.bfloat16, 'dout')
+  _req(y, torch.bfloat16, 'y')
   _req(addend, torch.bfloat16, 'addend', allow_none=True)
-  _req(dw, torch.float32, 'dw'); _req(saved, torch.float32, 'saved'); _req(coef, torch.float32, 'coef')
+  _req(saved, torch.float32, 'saved'); _req(coef, torch.float32, 'coef')
   _req(relu_bits, torch.uint8, 'relu_bits')
   n_out = d.n * d.ho * d.wo * d.cout
   if dout.numel() != n_out or y.numel() != n_out or relu_bits.numel() * 8 != n_out:
@@ -658,18 +655,9 @@ def conv_bwd_bnapply(d, x, dout, w_hwio, dw, y, relu_bits, saved, coef, addend=N
     raise ValueError('saved must be [4, Cout] and coef [3, Cout]')
   if addend is not None and addend.numel() != d.n * d.h * d.w * d.cin:
     raise ValueError('addend must have the shape of dx')
-  lib = _lib.load()
-  _count_macs('wgrad_macs', d)
-  _count_macs('dgrad_macs', d)
-  need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
-  ws = workspace(need, x.device, 'wg') if need else None
-  dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dout.device, 'dx')
-  check(lib.rigl_masked_conv2d_bwd_bnapply(C.byref(d), _ptr(x), _ptr(dout), _ptr(w_hwio), _ptr(addend), _ptr(dw), _ptr(dx), _ptr(ws),
-                                           ws.numel() if ws is not None else 0, _ptr(y), _ptr(relu_bits), _ptr(saved[0]),
-                                           _ptr(saved[1]), _ptr(coef), _stream()))
-  if on_dw_ready is not None:
-    on_dw_ready()
-  return dx
+  return _conv_bwd(d, x, dout, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_bwd_bnapply(
+      C.byref(d), _ptr(x), _ptr(dout), _ptr(w_hwio), _ptr(addend), _ptr(dw), pdx, ws, nws, _ptr(y), _ptr(relu_bits),
+      _ptr(saved[0]), _ptr(saved[1]), _ptr(coef), _stream()))
 
 
 def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, bn_fuse=None, addend_sub=None,
@@ -683,70 +671,44 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
   ``bn_fuse['partials']`` (fp32 [parts, 2, Cin]) for bn_bwd; left unset where the layer's kernels cannot.
   ``addend_sub`` = (sh, sw): ``addend`` is the gradient of the subsampled view x[:, ::sh, ::sw, :] -- bf16
   [n, ceil(h / sh), ceil(w / sw), cin] -- added at those pixels only (rigl_masked_conv2d_bwd_sub).
+  ``addend_bits`` (uint8, one bit per element of ``addend``): the addend counts only where its bit is set
+  (rigl_masked_conv2d_bwd_masked; a layer whose kernels have no masked form is refused by the library: RiglError).
   ``dx`` (optional, with ``need_dx``): the caller's bf16 [n, h, w, cin] tensor for dX instead of a fresh one."""
   if addend_sub is not None and tuple(addend_sub) == (1, 1):
     addend_sub = None
+  n_in = d.n * d.h * d.w * d.cin
+  both = mfma_supported(d) and mfma_dgrad_supported(d)
   if addend_bits is not None:
-    # ``addend_bits`` (uint8, one bit per element of ``addend``): the addend counts only where its bit is set
-    # (a layer whose kernels have no masked form is refused by the library: RiglError, RIGL_EUNSUPPORTED)
     if addend is None or not need_dx or bn_fuse is not None or addend_sub is not None:
       raise ValueError('addend_bits needs an addend and dX, and combines with neither bn_fuse nor addend_sub')
-    _req(x, torch.bfloat16, 'x'); _req(dy, torch.bfloat16, 'dy'); _req(dw, torch.float32, 'dw')
-    _req(addend, torch.bfloat16, 'addend'); _req(addend_bits, torch.uint8, 'addend_bits'); _req(w_hwio, torch.bfloat16, 'w_hwio')
-    if addend.numel() != d.n * d.h * d.w * d.cin or addend_bits.numel() * 8 != addend.numel():
+    _req(addend, torch.bfloat16, 'addend'); _req(addend_bits, torch.uint8, 'addend_bits')
+    if addend.numel() != n_in or addend_bits.numel() * 8 != n_in:
       raise ValueError('addend must have the shape of dx and addend_bits one bit per element of it')
-    lib = _lib.load()
-    _count_macs('wgrad_macs', d)
-    _count_macs('dgrad_macs', d)
-    need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
-    ws = workspace(need, x.device, 'wg') if need else None
-    dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dy.device, 'dx')
-    check(lib.rigl_masked_conv2d_bwd_masked(C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), _ptr(addend_bits), _ptr(dw),
-                                            _ptr(dx), _ptr(ws), ws.numel() if ws is not None else 0, _stream()))
-    if on_dw_ready is not None:
-      on_dw_ready()
-    return dx
+    return _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_bwd_masked(
+        C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), _ptr(addend_bits), _ptr(dw), pdx, ws, nws, _stream()))
   if addend_sub is not None:
     if addend is None or not need_dx or bn_fuse is not None:
       raise ValueError('addend_sub needs an addend and dX, and does not combine with bn_fuse')
-    if not (mfma_supported(d) and mfma_dgrad_supported(d)):
+    if not both:
       raise ValueError('addend_sub needs cin % 8 == cout % 8 == 0')
   if bn_fuse is not None:
     bn_fuse.pop('partials', None)
-    if not (need_dx and mfma_supported(d) and mfma_dgrad_supported(d) and dgrad_stats_parts(d) > 0):
+    if not (need_dx and both and dgrad_stats_parts(d) > 0):
       bn_fuse = None
   if not (mfma_supported(d) and (not need_dx or mfma_dgrad_supported(d))):
     conv_wgrad(d, x, dy, dw)
     if on_dw_ready is not None:
       on_dw_ready()
     return conv_dgrad(d, dy, w_hwio, dx=dx, addend=addend) if need_dx else None
-  _req(x, torch.bfloat16, 'x')
-  _req(dy, torch.bfloat16, 'dy')
-  _req(dw, torch.float32, 'dw')
   _req(addend, torch.bfloat16, 'addend', allow_none=True)
-  lib = _lib.load()
-  _count_macs('wgrad_macs', d)
-  if need_dx:
-    _count_macs('dgrad_macs', d)
-  need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
-  ws = workspace(need, x.device, 'wg') if need else None
-  if not need_dx:
-    dx = None
-  else:
-    _req(w_hwio, torch.bfloat16, 'w_hwio')
-    dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dy.device, 'dx')
-    if addend is not None and addend_sub is None and addend.numel() != dx.numel():
-      raise ValueError('addend must have the shape of dx')
   if addend_sub is not None:
     sh, sw = addend_sub
     if addend.numel() != d.n * (-(-d.h // sh)) * (-(-d.w // sw)) * d.cin:
       raise ValueError('addend must be [n, ceil(h / sh), ceil(w / sw), cin]')
-    check(lib.rigl_masked_conv2d_bwd_sub(
-        C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), int(sh), int(sw), _ptr(dw), _ptr(dx), _ptr(ws),
-        ws.numel() if ws is not None else 0, _stream()))
-    if on_dw_ready is not None:
-      on_dw_ready()
-    return dx
+    return _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_bwd_sub(
+        C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), int(sh), int(sw), _ptr(dw), pdx, ws, nws, _stream()))
+  if need_dx and addend is not None and addend.numel() != n_in:
+    raise ValueError('addend must have the shape of dx')
   bn = None
   if bn_fuse is not None:
     bx, saved = bn_fuse['x'], bn_fuse['saved']
@@ -754,18 +716,14 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
     _req(saved, torch.float32, 'bn saved')
     bits = bn_fuse.get('relu_bits')
     _req(bits, torch.uint8, 'bn relu_bits', allow_none=True)
-    if bx.numel() != dx.numel() or saved.numel() != 4 * d.cin:
+    if bx.numel() != n_in or saved.numel() != 4 * d.cin:
       raise ValueError('bn_fuse: x must have the shape of dx and saved must be [4, Cin]')
     part = torch.empty((dgrad_stats_parts(d), 2, d.cin), dtype=torch.float32, device=dy.device)
-    bn = _lib.BnReduceFuse(bx.data_ptr(), bits.data_ptr() if bits is not None else None, saved.data_ptr(),
-                           int(bool(bn_fuse['relu'])), part.data_ptr(), part.numel())
+    bn = C.byref(_lib.BnReduceFuse(bx.data_ptr(), bits.data_ptr() if bits is not None else None, saved.data_ptr(),
+                                   int(bool(bn_fuse['relu'])), part.data_ptr(), part.numel()))
     bn_fuse['partials'] = part
-  check(lib.rigl_masked_conv2d_bwd_bn(
-      C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), _ptr(dw), _ptr(dx), _ptr(ws),
-      ws.numel() if ws is not None else 0, C.byref(bn) if bn is not None else None, _stream()))
-  if on_dw_ready is not None:
-    on_dw_ready()
-  return dx
+  return _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_bwd_bn(
+      C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), _ptr(dw), pdx, ws, nws, bn, _stream()), need_dx=need_dx)
 
 
 def conv_bwd_grid(d, x, dy, w_hwio, dw, on_dw_ready=None, dx=None):
@@ -773,21 +731,10 @@ def conv_bwd_grid(d, x, dy, w_hwio, dw, on_dw_ready=None, dx=None):
   gradient at the pixels the conv read (zero elsewhere, never materialised) -- and writes the dense dW
   (rigl_masked_conv2d_bwd_grid).  The consumer is conv_bwd(..., addend=that, addend_sub=strides) of the tensor's other
   reader."""
-  _req(x, torch.bfloat16, 'x')
-  _req(dy, torch.bfloat16, 'dy')
-  _req(w_hwio, torch.bfloat16, 'w_hwio')
-  _req(dw, torch.float32, 'dw')
-  lib = _lib.load()
-  _count_macs('wgrad_macs', d)
-  _count_macs('dgrad_macs', ConvDesc(d.n, d.ho, d.wo, d.cin, d.ho, d.wo, d.cout, 1, 1, 1, 1, 0, 0))
-  need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
-  ws = workspace(need, x.device, 'wg') if need else None
-  dx = _out(dx, (d.n, d.ho, d.wo, d.cin), torch.bfloat16, dy.device, 'dx')      # (the caller's tensor, or a fresh one)
-  check(lib.rigl_masked_conv2d_bwd_grid(C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(dw), _ptr(dx), _ptr(ws),
-                                        ws.numel() if ws is not None else 0, _stream()))
-  if on_dw_ready is not None:
-    on_dw_ready()
-  return dx
+  grid = ConvDesc(d.n, d.ho, d.wo, d.cin, d.ho, d.wo, d.cout, 1, 1, 1, 1, 0, 0)      # (the stride-1 conv the dgrad amounts to)
+  return _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_bwd_grid(
+      C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(dw), pdx, ws, nws, _stream()),
+                   dx_shape=(d.n, d.ho, d.wo, d.cin), dgrad_desc=grid)
 
 
 # ----------------------------------------------------------------------------
@@ -814,9 +761,7 @@ def conv_fwd_relu(d, x, w_ohwi, y=None):
   if x.numel() != d.n * d.h * d.w * d.cin:
     raise ValueError('x must be [n, h, w, Cin] of the descriptor')
   _count_macs('fwd_macs', d)
-  if y is None:
-    y = torch.empty((d.n, d.ho, d.wo, d.cout), dtype=torch.bfloat16, device=x.device)
-  _req(y, torch.bfloat16, 'y')
+  y = _out(y, (d.n, d.ho, d.wo, d.cout), torch.bfloat16, x.device, 'y')
   lib = _lib.load()
   need = _plan_cached(d, 'ws_fwd', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 0))
   ws = workspace(need, x.device) if need else None
@@ -830,21 +775,10 @@ def conv_bwd_relu(d, x, dy, w_hwio, dw, on_dw_ready=None, dx=None):
   pool of one) -- rigl_masked_conv2d_bwd_relu.  ``dy`` must already carry this conv's own ReLU gate.  Returns dX."""
   _req(x, torch.bfloat16, 'x')
   _req(dy, torch.bfloat16, 'dy')
-  _req(w_hwio, torch.bfloat16, 'w_hwio')
-  _req(dw, torch.float32, 'dw')
   if x.numel() != d.n * d.h * d.w * d.cin or dy.numel() != d.n * d.ho * d.wo * d.cout:
     raise ValueError('x / dy must have the shapes of the descriptor')
-  lib = _lib.load()
-  _count_macs('wgrad_macs', d)
-  _count_macs('dgrad_macs', d)
-  need = _plan_cached(d, 'ws_wgrad', lambda: lib.rigl_conv2d_workspace_bytes(C.byref(d), 2))
-  ws = workspace(need, x.device, 'wg') if need else None
-  dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.bfloat16, dy.device, 'dx')        # (the caller's tensor, or a fresh one)
-  check(lib.rigl_masked_conv2d_bwd_relu(C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(dw), _ptr(dx), _ptr(ws),
-                                        ws.numel() if ws is not None else 0, _stream()))
-  if on_dw_ready is not None:
-    on_dw_ready()
-  return dx
+  return _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_bwd_relu(
+      C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(dw), pdx, ws, nws, _stream()))
 
 
 def relu_fwd(x, y=None):
@@ -888,28 +822,15 @@ def conv_fwd_f32(d, x, w_hwio, mask_bits=None, y=None):
 
 def conv_bwd_f32(d, x, dy, w_hwio, mask_bits, dw, need_dx=True, addend=None, on_dw_ready=None, dx=None):
   """fp32 twin of conv_bwd: dense dW (fp32 HWIO, overwritten) and -- when ``need_dx`` -- dX (+ ``addend``)."""
-  _req(x, torch.float32, 'x')
-  _req(dy, torch.float32, 'dy')
-  _req(dw, torch.float32, 'dw')
   _req(addend, torch.float32, 'addend', allow_none=True)
   _req(mask_bits, torch.int32, 'mask_bits', allow_none=True)
-  lib = _lib.load()
-  _count_macs('wgrad_macs', d)
-  need = _plan_cached(d, 'ws_wgrad_f32', lambda: lib.rigl_conv2d_wgrad_f32_workspace_bytes(C.byref(d)))
-  ws = workspace(need, x.device, 'wg32') if need else None
-  check(lib.rigl_masked_conv2d_wgrad_f32(C.byref(d), _ptr(x), _ptr(dy), _ptr(dw), _ptr(ws),
-                                         ws.numel() if ws is not None else 0, _stream()))
-  if on_dw_ready is not None:
-    on_dw_ready()
-  if not need_dx:
-    return None
-  _count_macs('dgrad_macs', d)
-  _req(w_hwio, torch.float32, 'w_hwio')
-  dx = _out(dx, (d.n, d.h, d.w, d.cin), torch.float32, dy.device, 'dx')         # (the caller's tensor, or a fresh one)
-  if addend is not None and addend.numel() != dx.numel():
+  if need_dx and addend is not None and addend.numel() != d.n * d.h * d.w * d.cin:
     raise ValueError('addend must have the shape of dx')
-  check(lib.rigl_masked_conv2d_dgrad_f32(C.byref(d), _ptr(dy), _ptr(w_hwio), _ptr(mask_bits), _ptr(addend), _ptr(dx),
-                                         _stream()))
+  dx = _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_wgrad_f32(
+      C.byref(d), _ptr(x), _ptr(dy), _ptr(dw), ws, nws, _stream()), need_dx=need_dx, f32=True)
+  if need_dx:       # (dW is complete and announced; the fp32 dgrad is a launch of its own)
+    check(_lib.load().rigl_masked_conv2d_dgrad_f32(C.byref(d), _ptr(dy), _ptr(w_hwio), _ptr(mask_bits), _ptr(addend), _ptr(dx),
+                                                   _stream()))
   return dx
 
 
@@ -957,6 +878,22 @@ def depthwise_wgrad(d, x, dy, dw):
 # ----------------------------------------------------------------------------
 # fused batch-norm (+ residual) (+ ReLU)
 # ----------------------------------------------------------------------------
+def _bn_plan(x, partials=None, need_ws=False):
+  """(rows, channels, workspace or None, parts) of a batch-norm call over the channel axis of bf16 ``x``: ``partials`` (checked:
+  fp32 [parts, 2, C]) stand in for the statistics pass, so the reduction workspace is only fetched without them or on ``need_ws``."""
+  _req(x, torch.bfloat16, 'x')
+  c = x.shape[-1]
+  m = x.numel() // c
+  parts = 0
+  if partials is not None:
+    _req(partials, torch.float32, 'partials')
+    if partials.dim() != 3 or partials.shape[1] != 2 or partials.shape[2] != c:
+      raise ValueError('partials must be [parts, 2, %d]' % c)
+    parts = partials.shape[0]
+  ws = workspace(_lib.load().rigl_bn_workspace_bytes(m, c), x.device) if (need_ws or partials is None) else None
+  return m, c, ws, parts
+
+
 def bn_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, relu,
            residual=None, partials=None, want_relu_bits=False):
   """x [..., C] bf16 contiguous.  Returns (y, saved) with saved = fp32 [4, C]
@@ -964,30 +901,19 @@ def bn_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, relu,
   conv_fwd(stats=True)) replaces the statistics pass over x.  With
   ``want_relu_bits`` returns (y, saved, bits): uint8 [numel/8], bit j of byte i =
   (y[8i+j] > 0), the ReLU mask the backward needs instead of y."""
-  _req(x, torch.bfloat16, 'x')
   _req(residual, torch.bfloat16, 'residual', allow_none=True)
   for t, nm in ((gamma, 'gamma'), (beta, 'beta')):
     _req(t, torch.float32, nm)
-  c = x.shape[-1]
-  m = x.numel() // c
-  lib = _lib.load()
+  m, c, ws, parts = _bn_plan(x, partials)
   y = torch.empty_like(x)
   saved = torch.empty((4, c), dtype=torch.float32, device=x.device)
   bits = torch.empty(x.numel() // 8, dtype=torch.uint8, device=x.device) \
       if (want_relu_bits and relu) else None
-  if partials is not None:
-    _req(partials, torch.float32, 'partials')
-    if partials.dim() != 3 or partials.shape[1] != 2 or partials.shape[2] != c:
-      raise ValueError('partials must be [parts, 2, C]')
-    ws = None
-  else:
-    ws = workspace(lib.rigl_bn_workspace_bytes(m, c), x.device)
-  check(lib.rigl_bn_fwd_stats(
+  check(_lib.load().rigl_bn_fwd_stats(
       m, c, _ptr(x), _ptr(residual), _ptr(gamma), _ptr(beta),
       _ptr(running_mean), _ptr(running_var), float(momentum), float(eps),
       int(bool(relu)), _ptr(y), _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]),
-      _ptr(saved[3]), _ptr(partials),
-      partials.shape[0] if partials is not None else 0, _ptr(bits), _ptr(ws),
+      _ptr(saved[3]), _ptr(partials), parts, _ptr(bits), _ptr(ws),
       ws.numel() if ws is not None else 0, _stream()))
   return (y, saved, bits) if want_relu_bits else (y, saved)
 
@@ -1000,62 +926,53 @@ def bn_bwd(x, y, dy, gamma, saved, relu, dgamma, dbeta, want_dres=False,
   tile, left by the dgrad epilogue that produced ``dy`` -- conv_bwd(bn_fuse=...)) replaces the
   reduction pass over dy and x."""
   _req(relu_bits, torch.uint8, 'relu_bits', allow_none=True)
-  _req(x, torch.bfloat16, 'x')
   _req(dy, torch.bfloat16, 'dy')
   _req(y, torch.bfloat16, 'y', allow_none=True)
-  c = x.shape[-1]
-  m = x.numel() // c
-  lib = _lib.load()
+  m, c, ws, parts = _bn_plan(x, partials, need_ws=True)
   dx = torch.empty_like(x)
   dres = torch.empty_like(x) if want_dres else None
-  ws = workspace(lib.rigl_bn_workspace_bytes(m, c), x.device)
-  _req(partials, torch.float32, 'partials', allow_none=True)
-  if partials is not None and (partials.dim() != 3 or partials.shape[1] != 2 or partials.shape[2] != c):
-    raise ValueError('partials must be [parts, 2, %d]' % c)
-  check(lib.rigl_bn_bwd_stats(m, c, _ptr(x), _ptr(y), _ptr(relu_bits), _ptr(dy), _ptr(gamma),
-                              _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]),
-                              _ptr(saved[3]), int(bool(relu)), _ptr(dx), _ptr(dres),
-                              _ptr(dgamma), _ptr(dbeta), _ptr(partials),
-                              partials.shape[0] if partials is not None else 0, _ptr(ws), ws.numel(),
-                              _stream()))
+  check(_lib.load().rigl_bn_bwd_stats(m, c, _ptr(x), _ptr(y), _ptr(relu_bits), _ptr(dy), _ptr(gamma),
+                                      _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]),
+                                      _ptr(saved[3]), int(bool(relu)), _ptr(dx), _ptr(dres),
+                                      _ptr(dgamma), _ptr(dbeta), _ptr(partials), parts, _ptr(ws), ws.numel(),
+                                      _stream()))
   return dx, dres
 
 
 def bn_bwd_reduce(x, dy, gamma, saved, relu, relu_bits, dgamma, dbeta):
   """bn_bwd without its apply pass (rigl_bn_bwd_reduce): dgamma / dbeta (fp32 [C]) are overwritten; returns coef, fp32 [3, C]
   (a = gamma * invstd, b = mean dz, c = mean dz * xhat), for conv_bwd_bnapply of the conv that produced ``x``."""
-  _req(x, torch.bfloat16, 'x')
   _req(dy, torch.bfloat16, 'dy')
   _req(relu_bits, torch.uint8, 'relu_bits', allow_none=not relu)
-  c = x.shape[-1]
-  m = x.numel() // c
+  m, c, ws, _ = _bn_plan(x)
   if dy.numel() != x.numel() or (relu and relu_bits.numel() * 8 != x.numel()):
     raise ValueError('dy must have the shape of x and relu_bits one bit per element of it')
-  lib = _lib.load()
   coef = torch.empty((3, c), dtype=torch.float32, device=x.device)
-  ws = workspace(lib.rigl_bn_workspace_bytes(m, c), x.device)
-  check(lib.rigl_bn_bwd_reduce(m, c, _ptr(x), _ptr(relu_bits) if relu else None, _ptr(dy), _ptr(gamma), _ptr(saved[0]),
-                               _ptr(saved[1]), int(bool(relu)), _ptr(dgamma), _ptr(dbeta), _ptr(coef), _ptr(ws), ws.numel(),
-                               _stream()))
+  check(_lib.load().rigl_bn_bwd_reduce(m, c, _ptr(x), _ptr(relu_bits) if relu else None, _ptr(dy), _ptr(gamma), _ptr(saved[0]),
+                                       _ptr(saved[1]), int(bool(relu)), _ptr(dgamma), _ptr(dbeta), _ptr(coef), _ptr(ws),
+                                       ws.numel(), _stream()))
   return coef
 
 
 # ----------------------------------------------------------------------------
 # stateless random tensors (TensorFlow bit layout)
 # ----------------------------------------------------------------------------
+def _i32(v):
+  """A Python int wrapped to int32 (TensorFlow's seeds)."""
+  v = int(v) & 0xFFFFFFFF
+  return v - (1 << 32) if v >= 1 << 31 else v
+
+
 def stateless_random(n, seed0, seed1, dist, scale=1.0, shift=0.0, device=None,
                      out=None):
   """fp32 [n] = tf.random.stateless_{uniform|normal}([n], seed=[seed0, seed1])
   * scale + shift.  seed0 / seed1 are int32 (Python ints are wrapped)."""
-  def i32(v):
-    v = int(v) & 0xFFFFFFFF
-    return v - (1 << 32) if v >= 1 << 31 else v
   if dist not in ('uniform', 'normal'):
     raise ValueError('dist must be "uniform" or "normal"')
   if out is None:
     out = torch.empty(int(n), dtype=torch.float32, device=device)
   _req(out, torch.float32, 'out')
-  check(_lib.load().rigl_stateless_random(_ptr(out), out.numel(), i32(seed0), i32(seed1),
+  check(_lib.load().rigl_stateless_random(_ptr(out), out.numel(), _i32(seed0), _i32(seed1),
                                           1 if dist == 'normal' else 0,
                                           float(scale), float(shift), _stream()))
   return out
@@ -1064,9 +981,6 @@ def stateless_random(n, seed0, seed1, dist, scale=1.0, shift=0.0, device=None,
 def stateless_random_batched(items, device):
   """items: [(n, seed0, seed1, 'uniform'|'normal', scale, shift)] -> list of fp32 [n] tensors (views of one
   allocation, each starting on a 256-byte boundary), filled by ONE launch (rigl_stateless_random_batched)."""
-  def i32(v):
-    v = int(v) & 0xFFFFFFFF
-    return v - (1 << 32) if v >= 1 << 31 else v
   if not items:
     return []
   offs, total = [], 0
@@ -1083,7 +997,7 @@ def stateless_random_batched(items, device):
     outs.append(t)
     arr[i].out = t.data_ptr() if int(n) else None
     arr[i].n = int(n)
-    arr[i].seed0, arr[i].seed1 = i32(s0), i32(s1)
+    arr[i].seed0, arr[i].seed1 = _i32(s0), _i32(s1)
     arr[i].dist = 1 if dist == 'normal' else 0
     arr[i].scale, arr[i].shift = float(scale), float(shift)
   check(_lib.load().rigl_stateless_random_batched(arr, len(items), _stream()))
@@ -1114,44 +1028,28 @@ def maxpool_bwd(d, dy, arg):
 def bn_statistics(x, gamma, beta, running_mean, running_var, momentum, eps, partials=None):
   """The statistics half of bn_fwd (no apply pass): returns saved = fp32 [4, C] (mean, invstd, scale, shift) and updates
   the moving averages (rigl_bn_fwd_statistics)."""
-  _req(x, torch.bfloat16, 'x')
-  c = x.shape[-1]
-  m = x.numel() // c
-  lib = _lib.load()
+  m, c, ws, parts = _bn_plan(x, partials)
   saved = torch.empty((4, c), dtype=torch.float32, device=x.device)
-  if partials is not None:
-    _req(partials, torch.float32, 'partials')
-    ws = None
-  else:
-    ws = workspace(lib.rigl_bn_workspace_bytes(m, c), x.device)
-  check(lib.rigl_bn_fwd_statistics(
+  check(_lib.load().rigl_bn_fwd_statistics(
       m, c, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), float(momentum), float(eps),
-      _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]), _ptr(saved[3]), _ptr(partials),
-      partials.shape[0] if partials is not None else 0, _ptr(ws), ws.numel() if ws is not None else 0, _stream()))
+      _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]), _ptr(saved[3]), _ptr(partials), parts, _ptr(ws),
+      ws.numel() if ws is not None else 0, _stream()))
   return saved
 
 
 def bn_add_bn_fwd(x, x2, saved2, gamma, beta, running_mean, running_var, momentum, eps, relu, partials=None):
   """relu?(bn(x) + bn2(x2)) in one apply pass; ``saved2`` = bn_statistics(x2, ...).  Returns (y, saved, relu_bits|None)."""
-  _req(x, torch.bfloat16, 'x')
   _req(x2, torch.bfloat16, 'x2')
   if x2.shape != x.shape:
     raise ValueError('x2 must have the shape of x')
-  c = x.shape[-1]
-  m = x.numel() // c
-  lib = _lib.load()
+  m, c, ws, parts = _bn_plan(x, partials)
   y = torch.empty_like(x)
   saved = torch.empty((4, c), dtype=torch.float32, device=x.device)
   bits = torch.empty(x.numel() // 8, dtype=torch.uint8, device=x.device) if relu else None
-  if partials is not None:
-    _req(partials, torch.float32, 'partials')
-    ws = None
-  else:
-    ws = workspace(lib.rigl_bn_workspace_bytes(m, c), x.device)
-  check(lib.rigl_bn_add_bn_fwd(
+  check(_lib.load().rigl_bn_add_bn_fwd(
       m, c, _ptr(x), _ptr(x2), _ptr(saved2[2]), _ptr(saved2[3]), _ptr(gamma), _ptr(beta), _ptr(running_mean),
       _ptr(running_var), float(momentum), float(eps), int(bool(relu)), _ptr(y), _ptr(saved[0]), _ptr(saved[1]),
-      _ptr(saved[2]), _ptr(saved[3]), _ptr(partials), partials.shape[0] if partials is not None else 0, _ptr(bits),
+      _ptr(saved[2]), _ptr(saved[3]), _ptr(partials), parts, _ptr(bits),
       _ptr(ws), ws.numel() if ws is not None else 0, _stream()))
   return y, saved, bits
 

@@ -70,34 +70,83 @@ def _bn_fuse_publish(holder, req, dx):
     holder.partials, holder.dx_ptr = req['partials'], dx.data_ptr()
 
 
-class BnApplyHolder:
-  """Shared by the autograd nodes of a conv whose backward applies the backward of the batch norm BEHIND it on its dY load
-  (ops.conv_bwd_takes_bn_apply) and of that batch norm (workloads.nn._FusedBNFn).  Forward: the conv leaves it on its output
-  (attribute ``bn_apply``); the batch norm sets ``armed`` where it will skip its apply pass.  Backward: the batch norm runs
-  ops.bn_bwd_reduce, fills dout / y / bits / saved / coef and returns dout itself; the conv, one node later, takes them."""
-  __slots__ = ('armed', 'dout', 'y', 'bits', 'saved', 'coef')
+class _HandOver:
+  """A gradient handed from one autograd node to the next together with what the receiver needs to finish it.  Both nodes hold
+  the object from the forward on: the giver sets ``armed`` where it decides to hand over, calls ``fill(grad, *payload)`` in its
+  backward and returns ``grad`` itself; the receiver calls ``take`` on the gradient that arrives.  ``take`` raises where the two
+  disagree, or where autograd delivered another tensor (an accumulated or copied gradient): the payload is then not for it."""
+  __slots__ = ('armed', 'grad', 'payload')
+  knob = did = None        # (the subclass: the switch the messages name; what the giver did when it filled / when it did not)
 
   def __init__(self):
     self.armed = False
-    self.dout = self.y = self.bits = self.saved = self.coef = None
+    self.grad = self.payload = None
 
-  def fill(self, dout, y, bits, saved, coef):
-    self.dout, self.y, self.bits, self.saved, self.coef = dout, y, bits, saved, coef
+  def fill(self, grad, *payload):
+    self.grad, self.payload = grad, payload
 
-  def take(self, dy):
-    """The batch norm's products for the conv's backward, or None for the plain backward; raises where the two nodes
-    disagree (the gradient that arrived is then not what this conv's kernels would be run on)."""
-    filled = self.dout is not None
-    if self.armed != filled:
-      raise RuntimeError('bn_bwd_on_load: the batch norm %s its apply pass but the forward had decided otherwise'
-                         % ('skipped' if filled else 'ran'))
-    if not filled:
+  def take(self, grad):
+    """The payload for the receiver's backward, or None for its plain backward (neither side armed).  Empties the holder."""
+    filled, payload = self.grad, self.payload
+    self.grad = self.payload = None
+    if self.armed != (filled is not None):
+      raise RuntimeError('%s: the batch norm %s but the forward had decided otherwise' % (self.knob, self.did[filled is None]))
+    if filled is None:
       return None
-    if dy is not self.dout and (dy.data_ptr() != self.dout.data_ptr() or dy.shape != self.dout.shape or not dy.is_contiguous()):
-      raise RuntimeError('bn_bwd_on_load: the gradient that reached the conv is not the one the batch norm handed over')
-    got = (self.dout, self.y, self.bits, self.saved, self.coef)
-    self.dout = self.y = self.bits = self.saved = self.coef = None
-    return got
+    if grad is not filled and (grad is None or grad.data_ptr() != filled.data_ptr() or grad.shape != filled.shape
+                               or not grad.is_contiguous()):
+      raise RuntimeError('%s: the gradient that reached the conv is not the one the batch norm handed over' % self.knob)
+    return payload
+
+
+class BnApplyHolder(_HandOver):
+  """Between a conv whose backward applies the backward of the batch norm BEHIND it on its dY load
+  (ops.conv_bwd_takes_bn_apply) and that batch norm (workloads.nn._FusedBNFn).  Forward: the conv leaves it on its output
+  (attribute ``bn_apply``); the batch norm arms it where it will skip its apply pass.  Backward: the batch norm runs
+  ops.bn_bwd_reduce, fills (dout; y, bits, saved, coef) and returns dout itself; the conv, one node later, takes them."""
+  __slots__ = ()
+  knob, did = 'bn_bwd_on_load', ('skipped its apply pass', 'ran its apply pass')
+
+
+class MaskedAddendHolder(_HandOver):
+  """Between relu(bn3 + shortcut) (workloads.nn._FusedBNFn) and the conv whose ``fork`` made the shortcut and whose backward
+  masks its addend on the fly (takes_masked_addend).  Forward: ``fork`` leaves it on the alias (attribute ``masked_addend``);
+  the batch norm that takes the alias as its residual arms it.  Backward: the batch norm fills (dy; bits) and returns dy itself,
+  unmasked, as the residual's gradient; the fork's backward takes the ReLU bits."""
+  __slots__ = ()
+  knob, did = 'lazy_res_grad', ('handed the shortcut gradient over unmasked', 'wrote the masked shortcut gradient')
+
+
+def _conv_forward(lv, desc, x, want_stats):
+  """(y, statistics or None) of the layer's forward; fp32 activations (--precision=float32) run the validation kernels, which
+  have no statistics epilogue."""
+  if x.dtype == torch.float32:
+    return ops.conv_fwd_f32(desc, x, lv.weights.data.view(-1), _mask_bits(lv)), None
+  return ops.conv_fwd(desc, x, lv.ohwi, stats=True) if want_stats else (ops.conv_fwd(desc, x, lv.ohwi), None)
+
+
+def stats_outputs(ctx, want_stats, outs, parts, device):
+  """What a forward returns: ``outs`` (one tensor if it is alone), and with ``want_stats`` the batch-norm statistics ``parts``
+  behind them -- an empty tensor where the kernel left none -- as outputs autograd neither differentiates nor zero-fills."""
+  if not want_stats:
+    return outs if len(outs) > 1 else outs[0]
+  parts = tuple(p if p is not None else torch.empty(0, device=device) for p in parts)
+  ctx.mark_non_differentiable(*parts)
+  ctx.set_materialize_grads(False)
+  return outs + parts
+
+
+def _dw_ready(lv):
+  """The callback for "this layer's dW is enqueued": data parallel overlaps its all-reduce from there; None on one GPU."""
+  sync = getattr(lv.weights.graph, 'grad_sync', None)
+  return (lambda: sync.notify_layer_grad_ready(lv.weights)) if sync is not None else None
+
+
+def _dy_or_zeros(dy, d, x):
+  """The output gradient as the kernels want it; an unused output has a zero gradient."""
+  if dy is None:
+    return torch.zeros((d.n, d.ho, d.wo, d.cout), dtype=x.dtype, device=x.device)
+  return dy.contiguous()
 
 
 def _mask_bits(lv):
@@ -109,63 +158,39 @@ class _MaskedConvFn(torch.autograd.Function):
   """y = conv(x, mask*W) with dense dW written into lv.weights.grad."""
 
   @staticmethod
-  def forward(ctx, x, lv, desc, need_dx, want_stats=False, bn_holder=None, pending=None):
+  def forward(ctx, x, lv, desc, need_dx, want_stats=False, bn_holder=None, pending=None, apply_holder=None):
     ctx.lv, ctx.desc, ctx.need_dx = lv, desc, need_dx
-    ctx.bn_holder = bn_holder
+    ctx.bn_holder, ctx.apply_holder = bn_holder, apply_holder
     ctx.save_for_backward(x)
     if pending is not None:
       # x is the still EMPTY output of a batch norm that only finalised its statistics (workloads.nn.BatchNorm, consumer=):
       # this conv reads the pre-batch-norm tensor, applies scale / shift / ReLU on its operand load and fills x on the way
       out = ops.conv_fwd_bnrelu(desc, pending.x, pending.saved, lv.ohwi, x, stats=want_stats)
-      if not want_stats:
-        return out
-      y, part = out
-      ctx.mark_non_differentiable(part)
-      ctx.set_materialize_grads(False)
-      return y, part
-    if x.dtype == torch.float32:         # --precision=float32: the fp32 validation kernels, no statistics epilogue
-      y = ops.conv_fwd_f32(desc, x, lv.weights.data.view(-1), _mask_bits(lv))
-      if not want_stats:
-        return y
-      part = torch.empty(0, device=x.device)
-      ctx.mark_non_differentiable(part)
-      ctx.set_materialize_grads(False)
-      return y, part
-    if not want_stats:
-      return ops.conv_fwd(desc, x, lv.ohwi)
-    y, part = ops.conv_fwd(desc, x, lv.ohwi, stats=True)
-    if part is None:
-      part = torch.empty(0, device=x.device)
-    ctx.mark_non_differentiable(part)
-    ctx.set_materialize_grads(False)     # no zero-filled "gradient" for the statistics output
-    return y, part
+      y, part = out if want_stats else (out, None)
+    else:
+      y, part = _conv_forward(lv, desc, x, want_stats)
+    return stats_outputs(ctx, want_stats, (y,), (part,), x.device)
 
   @staticmethod
   def backward(ctx, dy, _dpart=None):
     (x,) = ctx.saved_tensors
     lv, d = ctx.lv, ctx.desc
-    if dy is None:                       # output unused: zero gradient
-      dy = torch.zeros((d.n, d.ho, d.wo, d.cout), dtype=x.dtype, device=x.device)
-    dy = dy.contiguous()
+    dy = _dy_or_zeros(dy, d, x)
     # dense dL/d(mask*W), fp32 HWIO, into this layer's slice of the G arena, and dX -- one call
-    sync = getattr(lv.weights.graph, 'grad_sync', None)
-    ready = (lambda: sync.notify_layer_grad_ready(lv.weights)) if sync is not None else None   # DP: overlap the all-reduce
+    ready = _dw_ready(lv)
     if x.dtype == torch.float32:
       dx = ops.conv_bwd_f32(d, x, dy, lv.weights.data.view(-1), _mask_bits(lv), lv.weights.grad.view(-1),
                             need_dx=ctx.need_dx, on_dw_ready=ready)
-      return dx, None, None, None, None, None, None
-    # (MaskedConv2d.__call__ leaves the holder on the node once the forward has run: it is not an input of the function)
-    apply_holder = getattr(ctx, 'apply_holder', None)
-    got = apply_holder.take(dy) if apply_holder is not None else None
+      return (dx,) + (None,) * 7
+    got = ctx.apply_holder.take(dy) if ctx.apply_holder is not None else None
     if got is not None:
       # dy is the gradient w.r.t. the OUTPUT of the batch norm behind this conv: its apply pass runs on this backward's dY load
-      dout, y, bits, saved, coef = got
-      dx = ops.conv_bwd_bnapply(d, x, dout, lv.hwio, lv.weights.grad.view(-1), y, bits, saved, coef, on_dw_ready=ready)
-      return dx, None, None, None, None, None, None
+      dx = ops.conv_bwd_bnapply(d, x, dy, lv.hwio, lv.weights.grad.view(-1), *got, on_dw_ready=ready)
+      return (dx,) + (None,) * 7
     req = _bn_fuse_request(ctx.bn_holder, ctx.need_dx)
     dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=ctx.need_dx, on_dw_ready=ready, bn_fuse=req)
     _bn_fuse_publish(ctx.bn_holder, req, dx)
-    return dx, None, None, None, None, None, None
+    return (dx,) + (None,) * 7
 
 
 class _MaskedConvReluFn(torch.autograd.Function):
@@ -188,9 +213,7 @@ class _MaskedConvReluFn(torch.autograd.Function):
   def backward(ctx, dy):
     (x,) = ctx.saved_tensors
     lv, d = ctx.lv, ctx.desc
-    dy = dy.contiguous()
-    sync = getattr(lv.weights.graph, 'grad_sync', None)
-    ready = (lambda: sync.notify_layer_grad_ready(lv.weights)) if sync is not None else None
+    dy, ready = _dy_or_zeros(dy, d, x), _dw_ready(lv)
     if ctx.need_dx and ctx.gate_input:
       dx = ops.conv_bwd_relu(d, x, dy, lv.hwio, lv.weights.grad.view(-1), on_dw_ready=ready)
     else:
@@ -206,54 +229,37 @@ class _MaskedConvForkFn(torch.autograd.Function):
   separate AddN pass autodiff would emit (rigl_masked_conv2d_dgrad_acc)."""
 
   @staticmethod
-  def forward(ctx, x, lv, desc, want_stats=False, bn_holder=None):
+  def forward(ctx, x, lv, desc, want_stats=False, bn_holder=None, addend_holder=None):
     ctx.lv, ctx.desc = lv, desc
-    ctx.bn_holder = bn_holder
+    ctx.bn_holder, ctx.addend_holder = bn_holder, addend_holder
     ctx.save_for_backward(x)
-    if x.dtype == torch.float32:
-      y = ops.conv_fwd_f32(desc, x, lv.weights.data.view(-1), _mask_bits(lv))
-      if not want_stats:
-        return y, x.view_as(x)
-      part = torch.empty(0, device=x.device)
-      ctx.mark_non_differentiable(part)
-      ctx.set_materialize_grads(False)
-      return y, x.view_as(x), part
-    if not want_stats:
-      return ops.conv_fwd(desc, x, lv.ohwi), x.view_as(x)
-    y, part = ops.conv_fwd(desc, x, lv.ohwi, stats=True)
-    if part is None:
-      part = torch.empty(0, device=x.device)
-    ctx.mark_non_differentiable(part)
-    ctx.set_materialize_grads(False)
-    return y, x.view_as(x), part
+    y, part = _conv_forward(lv, desc, x, want_stats)
+    return stats_outputs(ctx, want_stats, (y, x.view_as(x)), (part,), x.device)
 
   @staticmethod
   def backward(ctx, dy, dalias, _dpart=None):
     (x,) = ctx.saved_tensors
     lv, d = ctx.lv, ctx.desc
-    if dy is None:
-      dy = torch.zeros((d.n, d.ho, d.wo, d.cout), dtype=x.dtype, device=x.device)
-    dy = dy.contiguous()
+    dy, ready = _dy_or_zeros(dy, d, x), _dw_ready(lv)
     if dalias is not None:
       dalias = dalias.contiguous()
-    sync = getattr(lv.weights.graph, 'grad_sync', None)
-    ready = (lambda: sync.notify_layer_grad_ready(lv.weights)) if sync is not None else None
     if x.dtype == torch.float32:
       dx = ops.conv_bwd_f32(d, x, dy, lv.weights.data.view(-1), _mask_bits(lv), lv.weights.grad.view(-1),
                             need_dx=True, addend=dalias, on_dw_ready=ready)
-      return dx, None, None, None, None
-    # the alias' gradient may arrive unmasked with the ReLU bits it still has to pass (workloads.nn._FusedBNFn, lazy_res_grad)
-    lazy = ops.LAZY_ADDEND_BITS.pop(dalias.data_ptr(), None) if dalias is not None else None
-    if lazy is not None:
-      dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=True, addend=dalias, addend_bits=lazy[0],
+      return (dx,) + (None,) * 5
+    # the alias' gradient may arrive unmasked with the ReLU bits it still has to pass (workloads.nn._FusedBNFn): only as the very
+    # tensor the batch norm handed over -- anything else (autograd summed or copied it) raises instead of being added unmasked
+    got = ctx.addend_holder.take(dalias) if ctx.addend_holder is not None else None
+    if got is not None:
+      dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=True, addend=dalias, addend_bits=got[0],
                         on_dw_ready=ready)
-      return dx, None, None, None, None
+      return (dx,) + (None,) * 5
     # dx = this conv's dgrad + the alias' gradient is the COMPLETE gradient of the forked tensor: the producing batch
     # norm's reductions are taken on it
     req = _bn_fuse_request(ctx.bn_holder, True)
     dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=True, addend=dalias, on_dw_ready=ready, bn_fuse=req)
     _bn_fuse_publish(ctx.bn_holder, req, dx)
-    return dx, None, None, None, None
+    return (dx,) + (None,) * 5
 
 
 class _MaskedConvPairFn(torch.autograd.Function):
@@ -269,31 +275,19 @@ class _MaskedConvPairFn(torch.autograd.Function):
   def forward(ctx, x, lv_s, d_s, lv_m, d_m, want_stats):
     ctx.lv_s, ctx.d_s, ctx.lv_m, ctx.d_m = lv_s, d_s, lv_m, d_m
     ctx.save_for_backward(x)
-    if not want_stats:
-      return ops.conv_fwd(d_s, x, lv_s.ohwi), ops.conv_fwd(d_m, x, lv_m.ohwi)
-    ys, ps = ops.conv_fwd(d_s, x, lv_s.ohwi, stats=True)
-    ym, pm = ops.conv_fwd(d_m, x, lv_m.ohwi, stats=True)
-    ps = ps if ps is not None else torch.empty(0, device=x.device)
-    pm = pm if pm is not None else torch.empty(0, device=x.device)
-    ctx.mark_non_differentiable(ps, pm)
-    ctx.set_materialize_grads(False)
-    return ys, ym, ps, pm
+    ys, ps = _conv_forward(lv_s, d_s, x, want_stats)
+    ym, pm = _conv_forward(lv_m, d_m, x, want_stats)
+    return stats_outputs(ctx, want_stats, (ys, ym), (ps, pm), x.device)
 
   @staticmethod
   def backward(ctx, dys, dym, _dps=None, _dpm=None):
     (x,) = ctx.saved_tensors
     lv_s, d_s, lv_m, d_m = ctx.lv_s, ctx.d_s, ctx.lv_m, ctx.d_m
-    if dys is None:
-      dys = torch.zeros((d_s.n, d_s.ho, d_s.wo, d_s.cout), dtype=torch.bfloat16, device=x.device)
-    if dym is None:
-      dym = torch.zeros((d_m.n, d_m.ho, d_m.wo, d_m.cout), dtype=torch.bfloat16, device=x.device)
-    dys, dym = dys.contiguous(), dym.contiguous()
-    sync = getattr(lv_s.weights.graph, 'grad_sync', None)
-    ready = (lambda lv: (lambda: sync.notify_layer_grad_ready(lv.weights))) if sync is not None else (lambda lv: None)
+    dys, dym = _dy_or_zeros(dys, d_s, x), _dy_or_zeros(dym, d_m, x)
     # the strided conv: dW from x as it lies; dX on its own grid only (= the dgrad of a stride-1 1x1 conv over that grid)
-    dxs = ops.conv_bwd_grid(d_s, x, dys, lv_s.hwio, lv_s.weights.grad.view(-1), on_dw_ready=ready(lv_s))
+    dxs = ops.conv_bwd_grid(d_s, x, dys, lv_s.hwio, lv_s.weights.grad.view(-1), on_dw_ready=_dw_ready(lv_s))
     dx = ops.conv_bwd(d_m, x, dym, lv_m.hwio, lv_m.weights.grad.view(-1), need_dx=True, addend=dxs,
-                      addend_sub=(d_s.stride_h, d_s.stride_w), on_dw_ready=ready(lv_m))
+                      addend_sub=(d_s.stride_h, d_s.stride_w), on_dw_ready=_dw_ready(lv_m))
     return dx, None, None, None, None, None
 
 
@@ -406,14 +400,13 @@ class MaskedConv2d(_Layer):
     # the batch norm behind this conv may leave its backward apply pass to this conv's backward (workloads.nn.BatchNorm)
     apply_holder = BnApplyHolder() if (need_dx and x.dtype == torch.bfloat16 and x.is_cuda and ops.conv_bwd_takes_bn_apply(d)) else None
     if not bn_stats:
-      y = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, False, holder, pending)
+      y = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, False, holder, pending, apply_holder)
     else:
-      y, part = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, True, holder, pending)
+      y, part = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, True, holder, pending, apply_holder)
       if part.numel():
         y.bn_partials = part
     if apply_holder is not None and y.grad_fn is not None:
-      y.grad_fn.apply_holder = apply_holder          # the conv's autograd node (its ctx) ...
-      y.bn_apply = apply_holder                      # ... and the batch norm that reads y share it
+      y.bn_apply = apply_holder                      # the conv's autograd node and the batch norm that reads y share it
     return y
 
   def conv_relu(self, x, gate_input=True):
@@ -457,11 +450,13 @@ class MaskedConv2d(_Layer):
     self.graph.refresh_shadows()
     n, h, w, _ = x.shape
     holder = _bn_source(x)
-    if not bn_stats:
-      return _MaskedConvForkFn.apply(x.contiguous(), self.vars, self.desc_for(n, h, w), False, holder)
-    y, alias, part = _MaskedConvForkFn.apply(x.contiguous(), self.vars, self.desc_for(n, h, w), True, holder)
-    if part.numel():
-      y.bn_partials = part
+    # relu(bn + alias) may hand the alias' gradient back unmasked with the ReLU bits (workloads.nn.BatchNorm arms this)
+    addend_holder = MaskedAddendHolder() if self.takes_masked_addend(x) else None
+    y, alias, *part = _MaskedConvForkFn.apply(x.contiguous(), self.vars, self.desc_for(n, h, w), bn_stats, holder, addend_holder)
+    if part and part[0].numel():
+      y.bn_partials = part[0]
+    if addend_holder is not None:
+      alias.masked_addend = addend_holder
     return y, alias
 
 

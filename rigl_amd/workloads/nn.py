@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from rigl_amd import variables as V
-from rigl_amd.pruning_layers import bias_tensor
+from rigl_amd.pruning_layers import bias_tensor, stats_outputs
 
 BATCH_NORM_DECAY = 0.9      # resnet_model.py:37
 BATCH_NORM_EPSILON = 1e-5   # resnet_model.py:38
@@ -64,20 +64,24 @@ class _FusedBNFn(torch.autograd.Function):
   the conv kernels' dW; autograd only routes dx (and the residual's grad)."""
 
   @staticmethod
-  def forward(ctx, x, residual, bn, relu, partials=None, holder=None, lazy_res_grad=False, defer=False, apply_holder=None):
+  def forward(ctx, x, residual, bn, relu, partials=None, holder=None, addend_holder=None, defer=False, apply_holder=None):
     from rigl_amd import ops  # pylint: disable=import-outside-toplevel
     x_in = x
     x = x.contiguous()
     res = residual.contiguous() if residual is not None else None
     ctx.bn, ctx.relu, ctx.has_res = bn, relu, res is not None
     ctx.holder = holder
-    ctx.lazy_res_grad = bool(lazy_res_grad) and relu and res is not None
+    # the residual is the alias of a conv's fork whose backward masks its addend on the fly (pruning_layers.MaskedAddendHolder,
+    # left on the alias): the backward then returns the output gradient itself, unmasked, as the residual's and fills the
+    # holder with the ReLU bits; decided (armed) here, and the fork's backward checks it
+    ctx.addend_holder = addend_holder if (_LAZY_RES_GRAD and relu and res is not None and ctx.needs_input_grad[1]) else None
+    if ctx.addend_holder is not None:
+      addend_holder.armed = True
     # the conv that produced x applies this batch norm's backward on its own dY load (pruning_layers.BnApplyHolder): only where
-    # the gradient of relu(bn + residual) leaves this node as it came in -- the residual's consumer masks on the fly
-    # (lazy_res_grad) -- so that nothing of the apply pass is left to write; decided here, and the conv's backward checks it
+    # the gradient of relu(bn + residual) leaves this node as it came in -- the residual's consumer masks on the fly -- so
+    # that nothing of the apply pass is left to write; decided here, and the conv's backward checks it
     ctx.apply_holder = None
-    if (apply_holder is not None and ctx.lazy_res_grad and not defer and x is x_in and ctx.needs_input_grad[0]
-        and ctx.needs_input_grad[1]):
+    if apply_holder is not None and ctx.addend_holder is not None and not defer and x is x_in and ctx.needs_input_grad[0]:
       ctx.apply_holder = apply_holder
       apply_holder.armed = True
     if defer:
@@ -124,14 +128,14 @@ class _FusedBNFn(torch.autograd.Function):
       # reductions + finalize only; the apply pass runs on the dY load of the conv that produced x, which receives dy itself
       coef = ops.bn_bwd_reduce(x, dy, bn.gamma.data, saved, True, bits, bn.gamma.grad, bn.beta.grad)
       ctx.apply_holder.fill(dy, x, bits, saved, coef)
-      ops.LAZY_ADDEND_BITS[dy.data_ptr()] = (bits, dy)
+      ctx.addend_holder.fill(dy, bits)
       return dy, dy, None, None, None, None, None, None, None
-    if ctx.lazy_res_grad and bits is not None and ctx.needs_input_grad[1]:
+    if ctx.addend_holder is not None:
       # the residual's consumer (the block's first conv, pruning_layers._MaskedConvForkFn) masks on the fly: its gradient is
       # dy where the ReLU was on, so dy itself travels with the ReLU bits and the masked copy is never written
       dx, _ = ops.bn_bwd(x, None, dy, bn.gamma.data, saved, ctx.relu, bn.gamma.grad, bn.beta.grad, want_dres=False,
                          relu_bits=bits, partials=part)
-      ops.LAZY_ADDEND_BITS[dy.data_ptr()] = (bits, dy)
+      ctx.addend_holder.fill(dy, bits)
       return dx, dy, None, None, None, None, None, None, None
     dx, dres = ops.bn_bwd(x, None, dy, bn.gamma.data, saved, ctx.relu,
                           bn.gamma.grad, bn.beta.grad,
@@ -207,9 +211,9 @@ class BatchNorm:
     self.scope = scope
     graph.modules[scope] = self          # creation order = TF's batch_normalization_<k> numbering
 
-  def __call__(self, x, is_training=True, relu=False, residual=None, lazy_res_grad=False, consumer=None):
-    """``lazy_res_grad``: the residual's ONLY other consumer is a masked conv whose backward takes its addend unmasked with
-    the ReLU bits (conv.takes_masked_addend): the backward then hands the output gradient itself to it.
+  def __call__(self, x, is_training=True, relu=False, residual=None, consumer=None):
+    """``residual``: where it is the alias of a MaskedConv2d.fork whose backward takes its addend unmasked with the ReLU bits
+    (the alias carries a pruning_layers.MaskedAddendHolder), the backward hands the output gradient itself to that conv.
     ``consumer``: the masked conv that is the ONLY reader of the output and is called on it next; where its forward takes the
     batch norm on its operand load (conv.takes_bn_input) only the statistics are finalised here and the conv fills the output."""
     if (self.fused and is_training and x.is_cuda and self.channels % 8 == 0
@@ -220,7 +224,8 @@ class BatchNorm:
       holder = _BnBwdHolder(relu)
       defer = bool(_BN_ON_LOAD and consumer is not None and relu and residual is None and consumer.takes_bn_input(x))
       apply_holder = getattr(x, 'bn_apply', None)   # left by the producing conv: its backward can take this one's apply pass
-      y = _FusedBNFn.apply(x, residual, self, relu, partials, holder, lazy_res_grad and _LAZY_RES_GRAD, defer, apply_holder)
+      addend_holder = getattr(residual, 'masked_addend', None)   # left by the fork that made the residual
+      y = _FusedBNFn.apply(x, residual, self, relu, partials, holder, addend_holder, defer, apply_holder)
       y.bn_ctx = holder                            # a masked conv that is this tensor's only consumer picks it up
       if defer:
         y.bn_pending = holder
@@ -299,14 +304,9 @@ class _DepthwiseFn(torch.autograd.Function):
     x = x.contiguous()
     ctx.layer, ctx.desc = layer, desc
     ctx.save_for_backward(x)
-    if not want_stats:
-      return ops.depthwise_fwd(desc, x, layer.weights.data.view(-1))
-    y, part = ops.depthwise_fwd(desc, x, layer.weights.data.view(-1), stats=True)
-    if part is None:
-      part = torch.empty(0, device=x.device)
-    ctx.mark_non_differentiable(part)
-    ctx.set_materialize_grads(False)
-    return y, part
+    out = ops.depthwise_fwd(desc, x, layer.weights.data.view(-1), stats=want_stats)
+    y, part = out if want_stats else (out, None)
+    return stats_outputs(ctx, want_stats, (y,), (part,), x.device)
 
   @staticmethod
   def backward(ctx, dy, _dpart=None):

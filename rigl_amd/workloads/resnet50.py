@@ -53,9 +53,6 @@ class _ConvFixedPadding:
   def fork(self, x, bn_stats=True):
     return self.conv.fork(x, bn_stats)
 
-  def takes_masked_addend(self, x):
-    return self.conv.takes_masked_addend(x)
-
   def takes_bn_input(self, x):
     return self.conv.takes_bn_input(x)
 
@@ -83,15 +80,14 @@ class _Bottleneck:
       # (a strided projection and conv1 as one autograd node: the projection's input gradient stays on its own grid)
       p, y = PL.conv_pair(self.proj.conv, self.c1.conv, x, bn_stats=True)
     else:
-      lazy = self.c1.takes_masked_addend(x)      # (the shortcut's gradient then reaches conv1 unmasked + the ReLU bits)
-      y, shortcut = self.c1.fork(x)
+      y, shortcut = self.c1.fork(x)              # (where conv1 takes it, the shortcut's gradient comes back unmasked + the ReLU bits)
     y = self.bn1(y, is_training, relu=True)
     y = self.bn2(self.c2(y), is_training, relu=True, consumer=self.c3)   # (RIGL_BN_ON_LOAD=1: conv3 applies it on its operand load)
     if self.proj is not None:
       # relu(bn3(conv3) + bn_proj(projection)) in one piece: neither the normalised shortcut nor the masked gradient
       # between the two batch norms is written
       return gnn.bn_add_bn_relu(self.bn3, self.c3(y), self.proj_bn, p, is_training)
-    return self.bn3(self.c3(y), is_training, relu=True, residual=shortcut, lazy_res_grad=lazy)   # relu(bn3 + shortcut)
+    return self.bn3(self.c3(y), is_training, relu=True, residual=shortcut)   # relu(bn3 + shortcut)
 
   def infer(self, x, p):
     """Eval forward with the frozen batch norms ``p`` (nn.infer_params): conv1 + bn1 + ReLU in its epilogue, conv2, conv3 with

@@ -92,7 +92,6 @@ def test_conv_node_raises_on_a_tampered_holder(how, monkeypatch):
       loss.backward()
     torch.cuda.synchronize()
   finally:
-    ops.LAZY_ADDEND_BITS.clear()
     ops.tune_unset('bwd1x1')
     ops.tune_unset('rs_masked_addend')
     ops.tune_unset('bn_bwd_on_load')

@@ -228,3 +228,64 @@ def test_precision_flag_maps_to_the_activation_dtype():
   assert gnn.activation_dtype('float32') == torch.float32
   with pytest.raises(ValueError):
     gnn.activation_dtype('float16')
+
+
+@pytest.mark.parametrize('cls,knob', (('BnApplyHolder', 'bn_bwd_on_load'), ('MaskedAddendHolder', 'lazy_res_grad')))
+def test_hand_over_between_autograd_nodes_checks_what_arrives(cls, knob):
+  """pruning_layers._HandOver, the protocol of both holders: take() gives the payload once for the very gradient that was
+  filled, None where neither side armed, and raises -- naming the switch -- on every disagreement."""
+  import torch
+  from rigl_amd import pruning_layers as PL
+  new = getattr(PL, cls)
+  g, bits = torch.zeros(2, 3), torch.ones(1, dtype=torch.uint8)
+  h = new()
+  assert h.take(g) is None and h.take(None) is None            # inert: nobody armed, nobody filled
+  h.armed = True
+  h.fill(g, bits, 'more')
+  got = h.take(g)
+  assert len(got) == 2 and got[0] is bits and got[1] == 'more'
+  assert h.grad is None and h.payload is None                  # emptied by take ...
+  with pytest.raises(RuntimeError, match=knob):                # ... so a second take finds it armed but not filled
+    h.take(g)
+  h.fill(g, bits)
+  assert h.take(g.view(2, 3))[0] is bits                       # the same memory, shape and layout under another tensor object
+  for other in (g.clone(), g.view(3, 2), g.t(), None):         # another tensor / shape / layout / no gradient at all
+    h.fill(g, bits)
+    with pytest.raises(RuntimeError, match=knob):
+      h.take(other)
+    assert h.grad is None and h.payload is None
+  h.armed = False                                              # filled though not armed
+  h.fill(g, bits)
+  with pytest.raises(RuntimeError, match=knob):
+    h.take(g)
+
+
+def test_conv_wrappers_refuse_a_short_output_buffer_before_any_library_call(monkeypatch):
+  """A caller-supplied y / dw one element short is a ValueError of the wrapper (ops._out), not a kernel writing past its end.
+  Host tensors stand in (the device check of ops._req is patched away); the library must not even be loaded."""
+  import torch
+  from rigl_amd import ops
+
+  class Loaded(Exception):
+    pass
+
+  def load():
+    raise Loaded()
+  monkeypatch.setattr(ops, '_req', lambda t, dtype, name, allow_none=False: None)  # pylint: disable=protected-access
+  monkeypatch.setattr(ops._lib, 'load', load)  # pylint: disable=protected-access
+  d = ops.conv_desc(2, 5, 5, 8, 16, 3, 3, 1, 1, 1, 5, 5)
+  x = torch.zeros(2, 5, 5, 8, dtype=torch.bfloat16)
+  dy = torch.zeros(2, 5, 5, 16, dtype=torch.bfloat16)
+  w = torch.zeros(9 * 8 * 16, dtype=torch.bfloat16)
+  ny, nw = 2 * 5 * 5 * 16, 9 * 8 * 16
+  with pytest.raises(ValueError, match='y must hold %d elements' % ny):
+    ops.conv_fwd(d, x, w, y=torch.zeros(ny - 1, dtype=torch.bfloat16))
+  with pytest.raises(ValueError, match='dw must hold %d elements' % nw):
+    ops.conv_wgrad(d, x, dy, dw=torch.zeros(nw - 1, dtype=torch.float32))
+  with pytest.raises(ValueError, match='dx must hold'):
+    ops.conv_dgrad(d, dy, w, dx=torch.zeros(2 * 5 * 5 * 8 + 1, dtype=torch.bfloat16))
+  # with buffers of the right size the same calls get as far as the library
+  with pytest.raises(Loaded):
+    ops.conv_fwd(d, x, w, y=torch.zeros(ny, dtype=torch.bfloat16))
+  with pytest.raises(Loaded):
+    ops.conv_wgrad(d, x, dy, dw=torch.zeros(nw, dtype=torch.float32))

@@ -14,7 +14,7 @@ DEV = 'cuda:0'
 
 @pytest.mark.skipif(not torch.cuda.is_available(), reason='needs a GPU')
 def test_resnet50_gradients_identical_with_and_without_the_masked_copy():
-  from rigl_amd import ops, sparse_optimizers as SO, sparse_utils, train, variables as V
+  from rigl_amd import ops, pruning_layers as PL, sparse_optimizers as SO, sparse_utils, train, variables as V
   from rigl_amd.workloads import nn as gnn, resnet50
   grads, used = [], []
   for lazy in (True, False):
@@ -27,16 +27,21 @@ def test_resnet50_gradients_identical_with_and_without_the_masked_copy():
     inner = train.MomentumOptimizer(0.05, 0.9, use_nesterov=True, graph=g)
     opt = SO.SparseRigLOptimizer(inner, 1, 25000, 100, drop_fraction=0.3, drop_fraction_anneal='cosine', noise_std=0.0)
     images, labels = resnet50.synthetic_batch(32, DEV, seed=5)     # (batch 32: the group-2 / group-3 conv1 layers are on bwdslice)
-    calls = [0]
-    conv_bwd0 = ops.conv_bwd
+    calls, holders = [0], []
+    conv_bwd0, init0 = ops.conv_bwd, PL.MaskedAddendHolder.__init__
 
     def counting(*a, **k):
       if k.get('addend_bits') is not None:
         calls[0] += 1
       return conv_bwd0(*a, **k)
+
+    def collecting(self):
+      init0(self)
+      holders.append(self)
     old = gnn._LAZY_RES_GRAD
     gnn._LAZY_RES_GRAD = lazy
     ops.conv_bwd = counting
+    PL.MaskedAddendHolder.__init__ = collecting
     try:
       loss = model.loss(images, labels, label_smoothing=0.1)
       opt.compute_gradients(loss)
@@ -44,7 +49,10 @@ def test_resnet50_gradients_identical_with_and_without_the_masked_copy():
     finally:
       gnn._LAZY_RES_GRAD = old
       ops.conv_bwd = conv_bwd0
-    assert not ops.LAZY_ADDEND_BITS, 'a lazy shortcut gradient was never taken by its conv'
+      PL.MaskedAddendHolder.__init__ = init0
+    assert holders and all(h.grad is None and h.payload is None for h in holders), \
+        'a lazy shortcut gradient was never taken by its conv'
+    assert sum(h.armed for h in holders) == calls[0], 'every armed hand-over is one masked backward, and no other'
     used.append(calls[0])
     grads.append((float(loss.detach()), g.G.detach().clone()))
   assert used[0] >= 6 and used[1] == 0, used        # groups 2 and 3: the non-first blocks' conv1 (3 + 5), if legal at this batch
