@@ -697,6 +697,41 @@ int rigl_stateless_random_batched(const RiglRandomItem* items, int32_t n_items,
                                   rigl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Dropout (the CIFAR WideResNet's bn -> relu -> Dropout(droprate) -> conv2,
+ * rigl/cifar_resnet/resnet_model.py:224-231).  TF's keep_mask =
+ * random_uniform(shape) >= rate; y = x * 1/(1-rate) * keep_mask, on the
+ * stateless stream above:
+ *   u       = tf.random.stateless_uniform([n], seed=[seed0, *step], float32),
+ *             the bits rigl_stateless_random(dist 0, scale 1, shift 0) writes
+ *   keep[i] = u[i] >= rate
+ *   scale   = 1.0f / (1.0f - rate)                       (fp32, on the host)
+ *   y[i]    = keep[i] ? round_to_dtype(f32(x[i]) * scale) : +0      (RNE)
+ *   keep_bits byte i/8, bit i%8 (LSB first) = keep[i]; ceil(n/8) bytes, the
+ *   unused high bits of the last byte are 0.
+ * A dropped element is a SELECT, not a multiply by 0: a dropped NaN, +-inf or
+ * -0 gives +0.  Kept NaN and inf pass through (a kept finite value whose
+ * product overflows rounds to inf).  rate == 0: y is bit-identical to x (quiet
+ * NaNs included) and every bit is 1.
+ * `step` is a DEVICE pointer to one int32, read by the kernel: a captured graph
+ * freezes kernel arguments, so a replay draws fresh masks only because
+ * rigl_dropout_advance (*step += 1 with int32 wrap-around, one single-lane
+ * launch) moves the counter inside the graph.  The backward reads the STORED
+ * bits, dx[i] = bit ? round_to_dtype(f32(dy[i]) * scale) : +0, and never
+ * regenerates them: the counter may have moved since the forward.
+ * dtype: 0 = bf16, 1 = fp32 (x / y, dy / dx).  16 bytes per lane where both
+ * tensors are 16-byte aligned, element-wise otherwise and for the last n % 8
+ * elements; the same bits either way.  Nothing past y[n-1] or past ceil(n/8)
+ * bytes of keep_bits is touched.  n == 0 succeeds without a launch; a rate
+ * that is NaN, < 0 or >= 1, or a NULL pointer with n > 0: RIGL_EINVAL.
+ * ---------------------------------------------------------------------- */
+int rigl_dropout_fwd(const void* x, void* y, uint8_t* keep_bits, int64_t n,
+                     int32_t dtype, float rate, int32_t seed0,
+                     const int32_t* step /* device */, rigl_stream_t stream);
+int rigl_dropout_bwd(const void* dy, const uint8_t* keep_bits, void* dx,
+                     int64_t n, int32_t dtype, float rate, rigl_stream_t stream);
+int rigl_dropout_advance(int32_t* step /* device */, rigl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Glue: max pooling, NHWC bf16 (tf.layers.max_pooling2d(3, 2, 'SAME') after the
  * stem, rigl/imagenet_resnet/resnet_model.py:637-644).  The descriptor is a
  * RiglConvDesc with cin == cout (% 8 == 0); padding explicit, windows clipped

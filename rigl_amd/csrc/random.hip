@@ -10,32 +10,12 @@
 // consecutive lane pairs.  One thread per group of 4 elements; HBM-bound write.
 // sinf / cosf / logf are ocml's (<= 2 ulp from glibc's, which TF's CPU kernel calls).
 #include "common.hpp"
+#include "philox.hpp"      // philox4x32_10, u32_to_float (shared with dropout.hip)
 
 namespace rigl {
 namespace krand {
 
 constexpr int THREADS = 256;
-constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-
-struct Philox { uint32_t c[4]; };
-
-__host__ __device__ inline Philox philox4x32_10(Philox ctr, uint32_t k0, uint32_t k1) {
-  for (int r = 0; r < 10; ++r) {
-    if (r) { k0 += W0; k1 += W1; }
-    const uint64_t p0 = (uint64_t)M0 * ctr.c[0], p1 = (uint64_t)M1 * ctr.c[2];
-    Philox n;
-    n.c[0] = (uint32_t)(p1 >> 32) ^ ctr.c[1] ^ k0;
-    n.c[1] = (uint32_t)p1;
-    n.c[2] = (uint32_t)(p0 >> 32) ^ ctr.c[3] ^ k1;
-    n.c[3] = (uint32_t)p0;
-    ctr = n;
-  }
-  return ctr;
-}
-
-__device__ __forceinline__ float u32_to_float(uint32_t x) {
-  return __uint_as_float((127u << 23) | (x & 0x7FFFFFu)) - 1.0f;
-}
 
 struct Args {
   float* out;

@@ -1005,6 +1005,62 @@ def stateless_random_batched(items, device):
 
 
 # ----------------------------------------------------------------------------
+# dropout (keep mask from the stateless stream, step counter on the device)
+# ----------------------------------------------------------------------------
+_DROPOUT_DTYPES = {torch.bfloat16: 0, torch.float32: 1}
+
+
+def _dropout_dtype(t, name):
+  _req(t, getattr(t, 'dtype', None), name)
+  if t.dtype not in _DROPOUT_DTYPES:
+    raise TypeError('%s: expected bfloat16 or float32, got %s' % (name, t.dtype))
+  return _DROPOUT_DTYPES[t.dtype]
+
+
+def dropout_fwd(x, rate, seed0, step, y=None, bits=None):
+  """(y, bits) = rigl_dropout_fwd: y = x / (1 - rate) where tf.random.stateless_uniform([n], seed=[seed0, step]) >= rate,
+  else +0; ``bits`` uint8 [ceil(n / 8)], bit i % 8 of byte i / 8 = element i kept.  ``step``: DEVICE int32 [1], read by the
+  kernel (``dropout_advance`` moves it on), so a replayed graph draws a fresh mask.  x: bf16 or fp32, any shape."""
+  dt = _dropout_dtype(x, 'x')
+  _req(step, torch.int32, 'step')
+  if step.numel() != 1:
+    raise ValueError('step must hold one int32')
+  n = x.numel()
+  if y is None:
+    y = torch.empty_like(x)
+  if bits is None:
+    bits = torch.empty((n + 7) // 8, dtype=torch.uint8, device=x.device)
+  _req(y, x.dtype, 'y')
+  _req(bits, torch.uint8, 'bits')
+  if y.numel() != n or bits.numel() < (n + 7) // 8:
+    raise ValueError('y must have the shape of x and bits ceil(n / 8) bytes')
+  check(_lib.load().rigl_dropout_fwd(_ptr(x), _ptr(y), _ptr(bits), n, dt, float(rate), _i32(seed0), _ptr(step), _stream()))
+  return y, bits
+
+
+def dropout_bwd(dy, bits, rate, dx=None):
+  """dx = dy / (1 - rate) where the forward's stored ``bits`` say kept, else +0 (rigl_dropout_bwd)."""
+  dt = _dropout_dtype(dy, 'dy')
+  _req(bits, torch.uint8, 'bits')
+  n = dy.numel()
+  if dx is None:
+    dx = torch.empty_like(dy)
+  _req(dx, dy.dtype, 'dx')
+  if dx.numel() != n or bits.numel() < (n + 7) // 8:
+    raise ValueError('dx must have the shape of dy and bits ceil(n / 8) bytes')
+  check(_lib.load().rigl_dropout_bwd(_ptr(dy), _ptr(bits), _ptr(dx), n, dt, float(rate), _stream()))
+  return dx
+
+
+def dropout_advance(step):
+  """step += 1 on the device (rigl_dropout_advance), once per training forward."""
+  _req(step, torch.int32, 'step')
+  if step.numel() != 1:
+    raise ValueError('step must hold one int32')
+  check(_lib.load().rigl_dropout_advance(_ptr(step), _stream()))
+
+
+# ----------------------------------------------------------------------------
 # max pooling (glue)
 # ----------------------------------------------------------------------------
 def maxpool_fwd(d, x):

@@ -241,6 +241,51 @@ class BatchNorm:
     return y
 
 
+class DropoutState:
+  """The dropout step counter of a model: one int32 on the DEVICE (``step``, initially 0), read by every dropout forward
+  kernel and advanced by ops.dropout_advance once per training forward.  It lives in device memory because a captured graph
+  (train.GraphedStep) freezes kernel arguments: a step passed by value would replay one mask for ever.  Readable for
+  checkpoints and tests.  ``bits_hook``: None, or a callable(seed0, bits) run right after a forward's kernel is enqueued
+  (inside a capture too, so a copy it makes is replayed with the step) -- for tests and debugging."""
+
+  def __init__(self, device):
+    self.step = torch.zeros(1, dtype=torch.int32, device=device)
+    self.bits_hook = None
+
+
+class _DropoutFn(torch.autograd.Function):
+  """y = x / (1 - rate) on the kept elements, +0 elsewhere (rigl_dropout_fwd / rigl_dropout_bwd).  Only the keep bits are
+  saved (1 bit per element); the backward reads them and never regenerates the mask -- the counter may have moved."""
+
+  @staticmethod
+  def forward(ctx, x, rate, seed0, state):
+    from rigl_amd import ops  # pylint: disable=import-outside-toplevel
+    y, bits = ops.dropout_fwd(x.contiguous(), rate, seed0, state.step)
+    ctx.rate = rate
+    ctx.save_for_backward(bits)
+    if state.bits_hook is not None:
+      state.bits_hook(seed0, bits)
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    from rigl_amd import ops  # pylint: disable=import-outside-toplevel
+    (bits,) = ctx.saved_tensors
+    return ops.dropout_bwd(dy.contiguous(), bits, ctx.rate), None, None, None
+
+
+def dropout(x, rate, seed0, state, is_training=True):
+  """tf.keras.layers.Dropout(rate) (resnet_model.py:224-231) with the keep mask of tf.random.stateless_uniform(seed=[seed0,
+  state.step]) >= rate.  Returns ``x`` itself where it does nothing (not training, or rate 0).  The output is a fresh tensor
+  that carries none of a batch norm's hand-over attributes (bn_ctx / bn_pending / bn_partials / bn_apply): the conv behind it
+  finds no batch-norm source and the batch norm in front takes its own backward reductions."""
+  if not is_training or rate == 0:
+    return x
+  if not 0.0 < rate < 1.0:
+    raise ValueError('dropout: rate must be in [0, 1), got %r' % (rate,))
+  return _DropoutFn.apply(x, float(rate), int(seed0), state)
+
+
 def eval_fused():
   """The eval forward (``infer``) takes the fused kernels -- the batch norms in the row-streaming epilogue / operand load, the stem
   tail in one pass -- unless knob "eval_fuse" is 0 (RIGL_EVAL_FUSE=0, or ops.tune_set): the separate passes, the same bits."""
