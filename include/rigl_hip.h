@@ -8,6 +8,15 @@
  *   - the caller owns every buffer and passes raw DEVICE pointers + sizes and
  *     the hipStream_t to enqueue on (as void*); nothing is allocated inside,
  *     scratch comes from a caller-provided workspace (`*_workspace_bytes`);
+ *     the workspace must start on a 256-byte boundary (every region inside it
+ *     is laid out in 256-byte units from its start) and hold at least the
+ *     queried number of bytes; its contents on entry do not matter, every
+ *     call initialises what it reads, and nothing is kept there between calls.
+ *     The queries follow the run-time knobs (rigl_tune_set) and the device:
+ *     ask again after changing a knob.  A workspace that is NULL or shorter
+ *     than the query, where the query is not 0, is refused with
+ *     RIGL_EWORKSPACE before anything is enqueued; the entry points that take
+ *     the argument pair without using it say so below;
  *   - every call only ENQUEUES work on `stream` (no hidden synchronisation);
  *   - return 0 on success, a negative RIGL_E* code otherwise; the message for
  *     the calling thread is available from rigl_last_error(); never throws;
@@ -331,6 +340,16 @@ typedef struct RiglConvDesc {
   int32_t pad_top, pad_left;
 } RiglConvDesc;
 
+/* which = 0: the forwards (rigl_masked_conv2d_fwd, _fwd_stats, _fwd_relu).  For the
+ * layers with cin <= 4 or cin % 8 != 0 it is the repacked operands and is
+ * required (RIGL_EWORKSPACE without it).  For every other layer it is the
+ * OPTIONAL scratch of a K-split plan (0 where the layer has none): with less
+ * than that, or NULL, the same forward runs unsplit -- the same sum in another
+ * order, never an error.
+ * which = 1: always 0.  rigl_masked_conv2d_dgrad and rigl_masked_conv2d_dgrad_acc
+ * take (workspace, workspace_bytes) and ignore them: pass NULL, 0.
+ * which = 2: rigl_masked_conv2d_wgrad and every rigl_masked_conv2d_bwd* form
+ * (the maximum over the plans the layer's backward can take), required.       */
 size_t rigl_conv2d_workspace_bytes(const RiglConvDesc* d, int32_t which /*0 fwd,1 dgrad,2 wgrad*/);
 int rigl_masked_conv2d_fwd(const RiglConvDesc* d, const rigl_bf16* x,
                            const rigl_bf16* w_ohwi, rigl_bf16* y,
@@ -372,7 +391,8 @@ int rigl_masked_conv2d_fwd_stats(const RiglConvDesc* d, const rigl_bf16* x,
  * parts are bit-identical to rigl_bn_fwd + rigl_masked_conv2d_fwd_stats.
  * Only where rigl_conv2d_fwd_takes_bn_input(d) == 1 (1x1 / stride-1 layers on
  * the row-streaming body, knob "bn_on_load"); else RIGL_EUNSUPPORTED.  The
- * statistics parts are those of rigl_conv2d_stats_parts(d).                 */
+ * statistics parts are those of rigl_conv2d_stats_parts(d).  The body has no
+ * K-split plan: (workspace, workspace_bytes) are ignored, pass NULL, 0.      */
 int32_t rigl_conv2d_fwd_takes_bn_input(const RiglConvDesc* d);
 int rigl_masked_conv2d_fwd_bnrelu(const RiglConvDesc* d, const rigl_bf16* x_pre,
                                   const float* scale_shift, rigl_bf16* a_out,
@@ -579,7 +599,9 @@ int rigl_masked_conv2d_wgrad_f32(const RiglConvDesc* d, const float* x,
  * shortcut`), rigl/imagenet_resnet/resnet_model.py:41-82, 456-501.  Not a
  * graded hot-path row; fused here because it is HBM-bound and sits inside the
  * images/s number.  y = relu?(gamma*(x-mean)*invstd + beta (+ residual)).
- * Statistics are deterministic (fixed-order partial sums).  c % 8 == 0.
+ * Statistics are deterministic (fixed-order partial sums; the kernel's own pass
+ * sums x - k and (x - k)^2 around a per-channel pivot k taken from three rows,
+ * so a channel far from zero keeps its variance).  c % 8 == 0.
  * save_* ([c] fp32 each) carry mean, 1/sqrt(var+eps), gamma*invstd and
  * beta-mean*gamma*invstd to the backward call.  running_* may be NULL.
  * Backward: the ReLU mask of (bn + residual) comes from relu_bits (1 bit per

@@ -68,8 +68,18 @@ __device__ __forceinline__ void ld8f(const float* __restrict__ p, float (&o)[8])
   o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
 }
 
+// The forward statistics are sums of SHIFTED data: per channel, q0 = sum (x - k) and q1 = sum (x - k)^2 with the pivot k = the
+// median of the channel's values in rows 0, M / 2 and M - 1 (a bf16 value; x - k is exact in fp32 for values of comparable size).
+// mean = k + q0 / M and var = q1 / M - (q0 / M)^2 then cancel like data whose mean is |mean - k| away from zero instead of
+// |mean|: E[x^2] - mean^2 accumulated in fp32 loses 2^-24 (mean / std)^2 of the variance per rounding, which on a channel 32
+// standard deviations from zero is six times the 1e-5 the variance is held to once a part sums enough rows to round at all
+// (C = 8: 256 row lanes, 1 792 rows and more in one part).  The median of three keeps one outlier row -- a lone spike in an
+// otherwise constant channel -- from becoming the pivot.  k_reduce<0> and k_fwd_finalize derive k by this one function from the
+// same three values, so it is the same number in both; a producer's partials (conv epilogues) are unshifted: k = 0.
+__device__ __forceinline__ float pivot3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
+
 // Reduction over rows of up to two per-channel quantities.
-//   MODE 0 (fwd stats): q0 = sum x, q1 = sum x^2
+//   MODE 0 (fwd stats): q0 = sum (x - k), q1 = sum (x - k)^2, k = the channel's pivot (above)
 //   MODE 1 (bwd)      : q0 = sum dz, q1 = sum dz * xhat,  dz = relu-masked dy
 // MSK: where the ReLU mask comes from -- 0 recomputed from x (scale, shift), 1 the saved output y,
 // 2 the 1-bit-per-element mask the forward left (1/16 of y's bytes).
@@ -96,6 +106,14 @@ __global__ __launch_bounds__(THREADS) void k_reduce(Geom G, const uint16_t* __re
       if (RELU && MSK == 0) { sc[j] = scale[cgi * 8 + j]; sh[j] = shift[cgi * 8 + j]; }
     }
   }
+  if (MODE == 0 && c_ok) {
+    float pa[8], pb[8], pc[8];
+    unpack8(*reinterpret_cast<const uint4*>(x + (int64_t)cgi * 8), pa);
+    unpack8(*reinterpret_cast<const uint4*>(x + (G.M / 2) * G.C + (int64_t)cgi * 8), pb);
+    unpack8(*reinterpret_cast<const uint4*>(x + (G.M - 1) * G.C + (int64_t)cgi * 8), pc);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) mu[j] = pivot3(pa[j], pb[j], pc[j]);
+  }
   if (c_ok) {
     // a part = every parts-th group of rpb rows ("bn_il", default: the grid streams one window of the tensors) or a
     // contiguous range of rows
@@ -108,7 +126,7 @@ __global__ __launch_bounds__(THREADS) void k_reduce(Geom G, const uint16_t* __re
       unpack8(*reinterpret_cast<const uint4*>(x + off), xv);
       if (MODE == 0) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { q0[j] += xv[j]; q1[j] = fmaf(xv[j], xv[j], q1[j]); }
+        for (int j = 0; j < 8; ++j) { const float d = xv[j] - mu[j]; q0[j] += d; q1[j] = fmaf(d, d, q1[j]); }
       } else {
         float dv[8], yv[8];
         unpack8(*reinterpret_cast<const uint4*>(dy + off), dv);
@@ -216,6 +234,7 @@ __device__ __forceinline__ void sum_partials(const Geom& G, const float* __restr
 // Forward finalize: mean / invstd, running statistics, fused scale & shift.
 template <int CL>
 __global__ __launch_bounds__(THREADS) void k_fwd_finalize(Geom G, const float* __restrict__ partial,
+                                                           const uint16_t* __restrict__ x /* the tensor k_reduce<0> summed; NULL: unshifted partials */,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            float* __restrict__ running_mean, float* __restrict__ running_var,
                                                            float momentum, float eps, float* __restrict__ save_mean,
@@ -225,8 +244,15 @@ __global__ __launch_bounds__(THREADS) void k_fwd_finalize(Geom G, const float* _
   sum_partials<CL>(G, partial, s0, s1, c, leader);
   if (!leader) return;
   const double m = (double)G.M;
-  const double mean = s0 / m;
-  double var = s1 / m - mean * mean;           // biased variance normalises (TF fused BN)
+  double k = 0.0;                              // the pivot the partials were shifted by (pivot3, as k_reduce<0> derives it)
+  if (x) {
+    const float a = __uint_as_float((uint32_t)x[c] << 16), b = __uint_as_float((uint32_t)x[(G.M / 2) * G.C + c] << 16),
+                e = __uint_as_float((uint32_t)x[(G.M - 1) * G.C + c] << 16);
+    k = (double)pivot3(a, b, e);
+  }
+  const double dm = s0 / m;
+  const double mean = k + dm;
+  double var = s1 / m - dm * dm;               // biased variance normalises (TF fused BN)
   if (var < 0.0) var = 0.0;
   const float invstd = (float)(1.0 / sqrt(var + (double)eps));
   save_mean[c] = (float)mean;
@@ -662,13 +688,13 @@ static int fwd_statistics(Geom& g, int32_t c, const rigl_bf16* x, const float* g
   // with 4 channels per workgroup a 64-channel layer is 16 workgroups each walking 49 rows per lane in dependent batches
   // (11.8 us on average over the step's 25 such finalizes; round 3)
   if (g.parts > 1024 && RIGL_TUNE("bn_fin1", 1) != 0)
-    hipLaunchKernelGGL(k_fwd_finalize<1>, dim3((unsigned)c), dim3(THREADS), 0, st, g, partial, gamma,
+    hipLaunchKernelGGL(k_fwd_finalize<1>, dim3((unsigned)c), dim3(THREADS), 0, st, g, partial, stats ? nullptr : reinterpret_cast<const uint16_t*>(x), gamma,
                        beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, save_scale, save_shift);
   else if (g.parts > 256)
-    hipLaunchKernelGGL(k_fwd_finalize<4>, dim3((unsigned)((c + 3) / 4)), dim3(THREADS), 0, st, g, partial, gamma,
+    hipLaunchKernelGGL(k_fwd_finalize<4>, dim3((unsigned)((c + 3) / 4)), dim3(THREADS), 0, st, g, partial, stats ? nullptr : reinterpret_cast<const uint16_t*>(x), gamma,
                        beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, save_scale, save_shift);
   else
-    hipLaunchKernelGGL(k_fwd_finalize<16>, dim3((unsigned)((c + 15) / 16)), dim3(THREADS), 0, st, g, partial, gamma,
+    hipLaunchKernelGGL(k_fwd_finalize<16>, dim3((unsigned)((c + 15) / 16)), dim3(THREADS), 0, st, g, partial, stats ? nullptr : reinterpret_cast<const uint16_t*>(x), gamma,
                        beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, save_scale, save_shift);
   return RIGL_OK;
 }

@@ -17,6 +17,14 @@ every setting of the set must reproduce the same expected bits -- so all bodies 
   python tests/k1_exact.py --set vgg            # test_vgg_gpu's 3x3 shapes, with and without the fused ReLU
   python tests/k1_exact.py --set dw | dw128     # depthwise: test_k3_k1_gpu's cases / MobileNet-v1's layers at batch 128
   python tests/k1_exact.py --set f32            # the fp32 twin on test_k1_fp32_gpu.KERNEL_CASES, dense and masked
+  python tests/k1_exact.py --set small --workspace exact   # the same walk on tests/wsguard.py's workspace, once per poison
+
+--workspace pool (the default) is the product's grow-only pool.  With --workspace exact every scratch request is carved
+exactly as long as the size query said, between two 1 MiB guards, and pre-filled with a poison (0x00, then 0xFF): every
+setting of every case runs once per poison against the SAME expected bits (they do not depend on the summation order, so
+a layer may split or not), and after every verified output the workspace guards must be intact as well.  The verdict then
+carries "workspace": {"mode": "exact", "poisons": [...], "requests": n, "guards": "intact", "max_bytes": b, "max_used": u}
+(max_used: the largest high-water mark, one past the last payload byte that differs from the poison -- reported only).
 
 Prints one line per case and regime and a final JSON verdict {"ok": true, "cases": n, "settings": m, "checks": c,
 "diff_bits": 0, "guards": "intact", "unwritten": 0, ...}; stops at the first failure with exit code 1.
@@ -92,6 +100,32 @@ class Tally:
   checks = 0
 
 
+class WS:
+  """--workspace exact: the installed tests/wsguard.GuardedWorkspace and the poisons to walk (None: the product's pool)."""
+  guard = None
+  poisons = ()
+  by_form = {}                             # verified output (without its setting) -> [requests, largest declared, largest used]
+
+
+def _poisons():
+  """Once per poison with the guard's poison set (no region is live when it changes); once, with None, on the pool."""
+  if WS.guard is None:
+    yield None
+    return
+  for p in WS.poisons:
+    WS.guard.check('before poison 0x%02X' % p)
+    WS.guard.poison = p
+    yield p
+  WS.guard.check('after the last poison')
+
+
+def _ws_check(name):
+  if WS.guard is not None:
+    for _, nbytes, used in WS.guard.check(name + ' [poison 0x%02X]' % WS.guard.poison):
+      t = WS.by_form.setdefault(name.split(' [')[0], [0, 0, 0])
+      t[0], t[1], t[2] = t[0] + 1, max(t[1], nbytes), max(t[2], used)
+
+
 def _g(shape, dtype):
   return E.guarded(shape, dtype, DEV)
 
@@ -100,6 +134,7 @@ def _verify(name, out, check, want):
   """Guards intact, nothing unwritten, and the output's bits == the expected bits."""
   check(name)
   E.assert_bits(name, E.got_bits(out), want)
+  _ws_check(name)
   Tally.checks += 1
 
 
@@ -181,7 +216,7 @@ def run_conv_case(case, seed, regime, settings):
     del ya, a_val
   del ref
   # ---- every setting must reproduce them ------------------------------------------------------------------------------
-  for knobs in settings:
+  for _, knobs in ((p, k) for p in _poisons() for k in settings):
     tag = lambda s: '%s [%s]' % (s, ' '.join('%s=%d' % kv for kv in sorted(knobs.items())) or 'default')   # noqa: E731
     try:
       for key, v in knobs.items():
@@ -293,28 +328,29 @@ def run_depthwise_case(case, seed, regime, settings):
   y2d = ref['y'].reshape(-1, C)
   tot = (y2d.sum(0), (y2d * y2d).sum(0)) if regime == 'low' else None
   del ref
-  y, chk, _ = _g((N, Ho, Wo, C), BF)
-  ops.depthwise_fwd(d, x, wd, y=y)
-  _verify('depthwise fwd', y, chk, want_y)
-  parts = int(lib.rigl_depthwise_conv2d_stats_parts(ctypes.byref(d)))
-  if parts > 0:
+  for _ in _poisons():
     y, chk, _ = _g((N, Ho, Wo, C), BF)
-    part, chkp, _ = _g((parts, 2, C), F32)
-    _, p2 = ops.depthwise_fwd(d, x, wd, stats=True, y=y, part=part)
-    assert p2 is part
-    _verify('depthwise fwd_stats.y', y, chk, want_y)
-    chkp('depthwise fwd_stats.part')
-    if tot is not None:
-      s = part.double().sum(0)
-      assert torch.equal(s[0], tot[0]), 'depthwise fwd_stats: the partials do not add up to the exact sum y'
-      assert torch.equal(s[1], tot[1]), 'depthwise fwd_stats: the partials do not add up to the exact sum y^2'
-    Tally.checks += 1
-  dx, chk, _ = _g((N, H, W, C), BF)
-  ops.depthwise_dgrad(d, dy, wd, dx=dx)
-  _verify('depthwise dgrad', dx, chk, want_dx)
-  dw, chk, _ = _g((k * k * C,), F32)
-  ops.depthwise_wgrad(d, x, dy, dw)
-  _verify('depthwise wgrad', dw, chk, want_dw)
+    ops.depthwise_fwd(d, x, wd, y=y)
+    _verify('depthwise fwd', y, chk, want_y)
+    parts = int(lib.rigl_depthwise_conv2d_stats_parts(ctypes.byref(d)))
+    if parts > 0:
+      y, chk, _ = _g((N, Ho, Wo, C), BF)
+      part, chkp, _ = _g((parts, 2, C), F32)
+      _, p2 = ops.depthwise_fwd(d, x, wd, stats=True, y=y, part=part)
+      assert p2 is part
+      _verify('depthwise fwd_stats.y', y, chk, want_y)
+      chkp('depthwise fwd_stats.part')
+      if tot is not None:
+        s = part.double().sum(0)
+        assert torch.equal(s[0], tot[0]), 'depthwise fwd_stats: the partials do not add up to the exact sum y'
+        assert torch.equal(s[1], tot[1]), 'depthwise fwd_stats: the partials do not add up to the exact sum y^2'
+      Tally.checks += 1
+    dx, chk, _ = _g((N, H, W, C), BF)
+    ops.depthwise_dgrad(d, dy, wd, dx=dx)
+    _verify('depthwise dgrad', dx, chk, want_dx)
+    dw, chk, _ = _g((k * k * C,), F32)
+    ops.depthwise_wgrad(d, x, dy, dw)
+    _verify('depthwise wgrad', dw, chk, want_dw)
   torch.cuda.synchronize()
   return fig
 
@@ -338,17 +374,18 @@ def run_f32_case(case, seed, regime, settings):
       for key, unit in (('y', op.uy), ('dx', op.udx)):
         assert float(ab[key].max()) / unit <= E.LIMIT, 'f32 dense: sum|a||b| over 2^24 units'
     del ab
-    y, chk, _ = _g((N, Ho, Wo, Cout), F32)
-    ops.conv_fwd_f32(d, op.x, op.w.reshape(-1), mb, y=y)
-    _verify('fwd_f32 ' + nm, y, chk, E.f32_pattern(ref['y']))
-    dx, chk, _ = _g((N, H, W, Cin), F32)
-    dw, chkw, _ = _g((n_w,), F32)
-    ops.conv_bwd_f32(d, op.x, op.dy, op.w.reshape(-1), mb, dw, need_dx=True, addend=op.add, dx=dx)
-    _verify('bwd_f32.dx ' + nm, dx, chk, E.f32_pattern(ref['dx'] + op.add.double()))
-    _verify('bwd_f32.dw ' + nm, dw, chkw, E.f32_pattern(ref['dw'].reshape(-1)))
-    dx, chk, _ = _g((N, H, W, Cin), F32)
-    ops.conv_bwd_f32(d, op.x, op.dy, op.w.reshape(-1), mb, dw, need_dx=True, dx=dx)
-    _verify('bwd_f32.dx (no addend) ' + nm, dx, chk, E.f32_pattern(ref['dx']))
+    for _ in _poisons():
+      y, chk, _ = _g((N, Ho, Wo, Cout), F32)
+      ops.conv_fwd_f32(d, op.x, op.w.reshape(-1), mb, y=y)
+      _verify('fwd_f32 ' + nm, y, chk, E.f32_pattern(ref['y']))
+      dx, chk, _ = _g((N, H, W, Cin), F32)
+      dw, chkw, _ = _g((n_w,), F32)
+      ops.conv_bwd_f32(d, op.x, op.dy, op.w.reshape(-1), mb, dw, need_dx=True, addend=op.add, dx=dx)
+      _verify('bwd_f32.dx ' + nm, dx, chk, E.f32_pattern(ref['dx'] + op.add.double()))
+      _verify('bwd_f32.dw ' + nm, dw, chkw, E.f32_pattern(ref['dw'].reshape(-1)))
+      dx, chk, _ = _g((N, H, W, Cin), F32)
+      ops.conv_bwd_f32(d, op.x, op.dy, op.w.reshape(-1), mb, dw, need_dx=True, dx=dx)
+      _verify('bwd_f32.dx (no addend) ' + nm, dx, chk, E.f32_pattern(ref['dx']))
     del ref
   torch.cuda.synchronize()
   return fig
@@ -363,7 +400,17 @@ def main():
   ap.add_argument('--batch', type=int, default=128)
   ap.add_argument('--only', type=int, default=-1)
   ap.add_argument('--regimes', default='low,round')
+  ap.add_argument('--workspace', default='pool', choices=['pool', 'exact'])
   a = ap.parse_args()
+  if a.workspace == 'pool':
+    return walk(a)
+  from tests import wsguard
+  WS.guard, WS.poisons = wsguard.GuardedWorkspace(), wsguard.POISONS
+  with wsguard.installed(WS.guard):
+    return walk(a)
+
+
+def walk(a):
   cases, settings = cases_for(a.set, a.batch), settings_for(a.set)
   run = run_depthwise_case if a.set in ('dw', 'dw128') else run_f32_case if a.set == 'f32' else run_conv_case
   t0, n = time.time(), 0
@@ -374,6 +421,7 @@ def main():
     for regime in a.regimes.split(','):
       try:
         fig = run(c, 100 + i, regime, settings)
+        _ws_check('end of case %d' % i)
       except AssertionError as e:
         print('FAIL case %d %s %s: %s' % (i, c, regime, e), flush=True)
         print(json.dumps({'ok': False, 'set': a.set, 'case': i, 'shape': list(c), 'regime': regime, 'error': str(e)[:600]}))
@@ -387,9 +435,14 @@ def main():
       print('ok case %d %s %s %s' % (i, c, regime, json.dumps(fig)), flush=True)
       torch.cuda.empty_cache()
     n += 1
-  print(json.dumps({'ok': True, 'set': a.set, 'cases': n, 'regimes': a.regimes.split(','), 'settings': len(settings),
-                    'checks': Tally.checks, 'diff_bits': 0, 'guards': 'intact', 'unwritten': 0, 'conditions': cond,
-                    'seconds': round(time.time() - t0, 1)}))
+  verdict = {'ok': True, 'set': a.set, 'cases': n, 'regimes': a.regimes.split(','), 'settings': len(settings),
+             'checks': Tally.checks, 'diff_bits': 0, 'guards': 'intact', 'unwritten': 0, 'conditions': cond,
+             'seconds': round(time.time() - t0, 1)}
+  if WS.guard is not None:
+    verdict['workspace'] = dict({'mode': 'exact', 'poisons': ['0x%02X' % p for p in WS.poisons], 'guards': 'intact'},
+                                **WS.guard.summary())
+    print('workspace by form [requests, largest declared bytes, largest high-water mark]: %s' % json.dumps(WS.by_form), flush=True)
+  print(json.dumps(verdict))
   return 0
 
 

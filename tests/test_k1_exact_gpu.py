@@ -60,6 +60,23 @@ def test_exact_bits_and_guard_bands(name, cases, settings, timeout):
 
 
 @pytest.mark.skipif(not torch.cuda.is_available(), reason='needs a GPU')
+@pytest.mark.parametrize('name,cases,settings,timeout', SETS, ids=[s[0] for s in SETS])
+def test_exact_bits_on_an_exact_guarded_poisoned_workspace(name, cases, settings, timeout):
+  """The same nine walks with --workspace exact (tests/wsguard.py): every scratch request exactly as long as the size query
+  said, between two 1 MiB guards, pre-filled with 0x00 and then 0xFF -- the expected bits do not depend on the summation
+  order, so they hold whether a layer splits or not, and a query that under-reports, a kernel that reads scratch it did
+  not initialise or a store outside the declared bytes all show.  Every set is walked in full, vgg included (both halves,
+  VGG16_SHAPES and C3_SHAPES: the fp64 references are made once per case and shared by the poisons, so the second poison
+  costs kernel time only).  The batch-128 sets are not repeated here."""
+  out = _run(['--set', name, '--workspace', 'exact'], timeout)
+  assert out['cases'] == cases and out['settings'] == settings
+  ws = out['workspace']
+  assert ws['mode'] == 'exact' and ws['poisons'] == ['0x00', '0xFF']
+  assert ws['guards'] == 'intact' and ws['requests'] > 0
+  assert 0 <= ws['max_used'] <= ws['max_bytes']
+
+
+@pytest.mark.skipif(not torch.cuda.is_available(), reason='needs a GPU')
 def test_resnet50_layer_shapes_at_batch_128():
   """The 23 distinct ResNet-50 conv shapes at the benchmarked batch: default selection and the all-generic setting."""
   out = _run(['--set', 'resnet50', '--batch', '128'], 2400)
