@@ -1406,6 +1406,57 @@ static int check_desc(const RiglConvDesc* d, const char* who) {
 static inline bool small_cin(const RiglConvDesc* d) { return (d->cin % 8) != 0 && d->cin > 4; }
 static inline int kpad(const RiglConvDesc* d) { return (d->kh * d->kw * d->cin + 31) / 32 * 32; }
 
+// ---- the tails every entry point shares
+static int check_workspace(const char* who, size_t need, const void* workspace, size_t workspace_bytes) {
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(RIGL_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+  return RIGL_OK;
+}
+// The end of a weight gradient: the partial slabs summed into dw (its first n_out of slab_elems outputs), unless the
+// kernel had a single split and wrote dw itself (slabs == dw); then the check of the launches.
+static int reduce_dw(const char* who, const float* slabs, float* dw, int64_t n_out, int64_t slab_elems, int splits,
+                     hipStream_t st) {
+  if (slabs != dw) launch_wgrad_reduce({slabs, dw, n_out, slab_elems, splits}, st);
+  RIGL_CHECK_LAUNCH(who);
+  return RIGL_OK;
+}
+
+// ---- the argument blocks of a layer as it lies in memory (the tiny- / small-Cin paths overwrite the operand they repack)
+static IgemmArgs fwd_args(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* w_ohwi, rigl_bf16* y, float* stats) {
+  IgemmArgs a = {};
+  a.A = x; a.B = w_ohwi; a.C = y; a.STATS = stats;
+  a.M = d->n * d->ho * d->wo; a.N = d->cout; a.Cred = d->cin; a.ldc = d->cout;
+  a.a_pix_stride = d->cin; a.KH = d->kh; a.KW = d->kw; a.RH = d->ho; a.RW = d->wo;
+  a.GH = d->h; a.GW = d->w; a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_top; a.pw = d->pad_left;
+  a.b_row_stride = d->kh * d->kw * d->cin; a.b_tap_stride = d->cin;
+  a.a_bytes = (uint32_t)((size_t)d->n * d->h * d->w * d->cin * 2);
+  a.b_bytes = (uint32_t)((size_t)d->kh * d->kw * d->cin * d->cout * 2);
+  return a;
+}
+static IgemmArgs dgrad_args(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio, const rigl_bf16* addend,
+                            rigl_bf16* dx) {
+  IgemmArgs a = {};
+  a.A = dy; a.B = w_hwio; a.C = dx; a.ADD = addend;
+  a.M = d->n * d->h * d->w; a.N = d->cin; a.Cred = d->cout; a.ldc = d->cin;
+  a.KH = d->kh; a.KW = d->kw; a.RH = d->h; a.RW = d->w; a.GH = d->ho; a.GW = d->wo;
+  a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_top; a.pw = d->pad_left;
+  a.b_row_stride = d->cout; a.b_tap_stride = d->cin * d->cout; a.a_pix_stride = d->cout;
+  a.a_bytes = (uint32_t)((size_t)d->n * d->ho * d->wo * d->cout * 2);
+  a.b_bytes = (uint32_t)((size_t)d->kh * d->kw * d->cin * d->cout * 2);
+  return a;
+}
+// (the plan fields -- tiles, splits, slab, OUT -- are the launcher's)
+static WgradArgs wgrad_args(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy) {
+  WgradArgs a = {};
+  a.interleave = RIGL_TUNE("wgrad_il", 1);
+  a.X = x; a.DY = dy; a.M = d->n * d->ho * d->wo; a.Cin = d->cin; a.Cout = d->cout; a.KH = d->kh; a.KW = d->kw;
+  a.H = d->h; a.W = d->w; a.Ho = d->ho; a.Wo = d->wo; a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_top; a.pw = d->pad_left;
+  a.x_bytes = (uint32_t)((size_t)d->n * d->h * d->w * d->cin * 2);
+  a.dy_bytes = (uint32_t)((size_t)a.M * d->cout * 2);
+  a.x_pix_stride = d->cin;
+  return a;
+}
+
 #include "convpp.hpp"
 #include "bwd1x1.hpp"
 #include "stem.hpp"
@@ -1413,21 +1464,19 @@ static inline int kpad(const RiglConvDesc* d) { return (d->kh * d->kw * d->cin +
 #include "rowstream.hpp"
 #include "bwdslice.hpp"
 
-// Scratch of the K-split ping-pong forward (convpp.hpp: pp_ksplit_ok): two fp32 partial tiles + a counter per tile.
-static size_t pp_ksplit_workspace(const RiglConvDesc* d) {
-  if (d->cin <= 4 || (d->cin % 8) || (d->cout % 8)) return 0;
-  IgemmArgs a = {};
-  a.M = d->n * d->ho * d->wo; a.N = d->cout; a.Cred = d->cin; a.a_pix_stride = d->cin; a.KH = d->kh; a.KW = d->kw;
-  a.RH = d->ho; a.RW = d->wo; a.GH = d->h; a.GW = d->w; a.sh = d->stride_h; a.sw = d->stride_w;
-  const PPPlan p = plan_pp<0>(a);
-  if (!pp_ksplit_ok(a, p)) return 0;
-  return (size_t)p.grid * 2 * p.bm * p.bn * 4 + align_up((size_t)p.grid * 4, 256);
-}
-
 struct WgradPlan { int tm, tn, tiles_ci, tiles_co, splits; int64_t slab; };
 // DMA ring depth of the tr kernel: 3 stages for the 128x128 tile (48 KB -> 3 workgroups/CU),
 // 4 for the smaller tiles (measured per layer).
 static int wgrad_stages(int tm, int tn) { return (tm == 2 && tn == 2) ? 3 : 4; }
+// A plan's tile as the template arguments <TM, TN, STAGES> of k_wgrad_tr and of the k_bwd_fused kernels that share its body:
+// LAUNCH_(TM, TN, STAGES, the caller's further arguments)
+#define RIGL_WGRAD_TILE(p_, LAUNCH_, ...)                                                                              \
+  {                                                                                                                    \
+    if ((p_).tm == 2 && (p_).tn == 2) { LAUNCH_(2, 2, 3, __VA_ARGS__) }                                                \
+    else if ((p_).tm == 2) { LAUNCH_(2, 1, 4, __VA_ARGS__) }                                                           \
+    else if ((p_).tn == 2) { LAUNCH_(1, 2, 4, __VA_ARGS__) }                                                           \
+    else { LAUNCH_(1, 1, 4, __VA_ARGS__) }                                                                             \
+  }
 static int num_cus() {
   static const int n = [] {
     int dev = 0, v = 0;
@@ -1472,9 +1521,103 @@ static WgradPlan plan_wgrad(int M, int cin, int cout, int taps, bool fused = fal
   return p;
 }
 
-// Tiny-Cin (stem) wgrad: the KH filter rows are folded into the channel axis (KH*cred = 224 "channels", one tap) so
-// the 128-channel tile is full and dY is read by 2 channel tiles instead of KH = 7 taps.
-static WgradPlan tiny_wgrad_plan(int M, int cred, int cout, int kh) { return plan_wgrad(M, kh * cred, cout, 1); }
+// The tiny- / small-Cin layers run their GEMMs on a repacked input at the head of the workspace: the image padded to 4
+// channels (tiny, geometry tg) or the im2col matrix (small).  From `rest` on the forward keeps its repacked filter, the
+// weight gradient its reduced [kh][cred][cout] image (tiny only: tmp_bytes) and then the slabs of plan wg.
+struct Repack { TinyGeom tg; size_t in_bytes, rest, w_bytes, tmp_bytes; WgradPlan wg; };
+static Repack repack_layout(const RiglConvDesc* d) {
+  Repack r = {};
+  const int M = d->n * d->ho * d->wo;
+  if (tiny_cin(d)) {
+    r.tg = tiny_geom(d);
+    r.in_bytes = (size_t)d->n * r.tg.hp * r.tg.wp * 4 * 2;
+    r.w_bytes = (size_t)d->cout * d->kh * r.tg.cred * 2;
+    // the KH filter rows are folded into the channel axis (KH*cred = 224 "channels", one tap) so the 128-channel tile is
+    // full and dY is read by 2 channel tiles instead of KH = 7 taps
+    r.wg = plan_wgrad(M, d->kh * r.tg.cred, d->cout, 1);
+    r.tmp_bytes = align_up((size_t)r.wg.slab * 4, 256);
+  } else {
+    r.in_bytes = (size_t)M * kpad(d) * 2;
+    r.w_bytes = (size_t)d->cout * kpad(d) * 2;
+    r.wg = plan_wgrad(M, kpad(d), d->cout, 1);
+  }
+  r.rest = align_up(r.in_bytes, 256);
+  return r;
+}
+
+// ---- which body runs a layer: DESIGN.md section 3 prints these three rule lists, the first rule that applies.  Each returns
+// the body of the layer and the plan its deciding rule computed; the launchers switch on it, the queries read it.
+enum FwdBody { FWD_STEM, FWD_TINY, FWD_IM2COL, FWD_RS, FWD_C3X3, FWD_PP, FWD_IGEMM };
+struct FwdSel { FwdBody body; RsPlan rs; PPPlan pp; };
+static FwdSel select_fwd(const RiglConvDesc* d, const IgemmArgs& a /* fwd_args(d, ...) */) {
+  FwdSel s = {};
+  // the ImageNet stem: the image patch of a 16 x 16 output tile resident in LDS, no padded copy (stem.hpp); other
+  // tiny-Cin layers on the igemm body over the image padded to 4 channels
+  if (tiny_cin(d)) s.body = stem_direct_legal(d) ? FWD_STEM : FWD_TINY;
+  else if (small_cin(d)) s.body = FWD_IM2COL;          // cin % 8 != 0: the igemm body over an explicit im2col matrix
+  else if (rs_use<0>(d, &s.rs)) s.body = FWD_RS;       // 1x1 / stride 1: rows streamed through registers against an LDS-stationary filter slice
+  else if (c3x3_use(d)) s.body = FWD_C3X3;             // 3x3, 64 -> 64: input patch resident in LDS, filter in registers (c3x3.hpp)
+  else if ((s.pp = plan_pp<0>(a)).variant) s.body = FWD_PP;   // long reductions: the 8-wave ping-pong body (+ K split: fwd_impl)
+  else s.body = FWD_IGEMM;
+  return s;
+}
+static int32_t fwd_stats_parts(const RiglConvDesc* d, const FwdSel& s) {
+  if (s.body == FWD_C3X3) return c3x3_stats_parts(d);     // c3x3.hpp: one partial per (persistent) workgroup
+  if (s.body == FWD_RS) return s.rs.gprime;               // rowstream.hpp: one partial per workgroup of a column slice
+  return (int32_t)(((int64_t)d->n * d->ho * d->wo + 127) / 128);     // one partial per 128-row output tile
+}
+// Scratch of the K-split ping-pong forward (convpp.hpp: pp_ksplit_ok): two fp32 partial tiles + a counter per tile.
+static size_t pp_ksplit_bytes(const PPPlan& p) { return (size_t)p.grid * 2 * p.bm * p.bn * 4 + align_up((size_t)p.grid * 4, 256); }
+static size_t pp_ksplit_workspace(const RiglConvDesc* d) {
+  if (d->cin <= 4 || (d->cin % 8) || (d->cout % 8)) return 0;
+  const IgemmArgs a = fwd_args(d, nullptr, nullptr, nullptr, nullptr);
+  const FwdSel s = select_fwd(d, a);
+  return s.body == FWD_PP && pp_ksplit_ok(a, s.pp) ? pp_ksplit_bytes(s.pp) : 0;
+}
+
+// dX.  The form of a call rules bodies out: this form admits these bodies.
+enum DxForm {
+  DXF_PLAIN,    // every body
+  DXF_IGEMM,    // a batch-norm block, or a subsampled addend to the stand-alone dgrad: only the igemm epilogue takes them
+  DXF_SUB,      // a subsampled addend inside the one-call backward: bwdslice (it rides in the same DMA ring: rows without
+                // an addend row read zeros), otherwise igemm
+  DXF_GRID,     // the own-grid dgrad of rigl_masked_conv2d_bwd_grid: the shared launches only (ping-pong, igemm)
+  DXF_MASKED    // a masked addend: bwdslice or the masked row-streaming dgrad, otherwise none (RIGL_EUNSUPPORTED)
+};
+enum DxBody { DX_BWD1X1, DX_BS, DX_RS, DX_C3X3, DX_PP, DX_IGEMM, DX_NONE };
+struct DxSel { DxBody body; BsPlan bs; RsPlan rs; PPPlan pp; };
+// A layer's dX must come from the same kernel whichever entry point computes it (rigl_masked_conv2d_dgrad or the one-call
+// backward): the bodies accumulate in different orders.  bwd1x1_refused: the single-pass kernel did not get its LDS (the
+// dX-only instantiation of the stand-alone dgrad, the weight-gradient one of the backward), so the rules after it decide.
+static DxSel select_dx(const RiglConvDesc* d, const IgemmArgs& a /* dgrad_args(d, ...) */, DxForm form = DXF_PLAIN,
+                       bool bwd1x1_refused = false) {
+  DxSel s = {};
+  const bool plain = form == DXF_PLAIN;
+  // the big-M 1x1 layers: dX (and dW) in a single pass over dY (bwd1x1.hpp)
+  if (plain && !bwd1x1_refused && bwd1x1_kind(d)) s.body = DX_BWD1X1;
+  // the many-input-channel 1x1 layers: the same single pass per 128-channel slice (bwdslice.hpp)
+  else if ((plain || form == DXF_SUB || form == DXF_MASKED) && bs_use(d, &s.bs)) s.body = DX_BS;
+  // dX[M][cin] = dY[M][cout] x W[cin][cout]^T, rows streamed (rowstream.hpp)
+  else if (plain ? rs_use<1>(d, &s.rs) : form == DXF_MASKED && rs_masked_use(d, &s.rs)) s.body = DX_RS;
+  else if (plain && c3x3_use(d)) s.body = DX_C3X3;     // 3x3, 64 -> 64 on resident patches (c3x3.hpp)
+  else if (form == DXF_MASKED) s.body = DX_NONE;
+  // long reductions whose weight gradient has 256-channel tiles: the 8-wave ping-pong body (convpp.hpp: plan_pp)
+  else if ((plain || form == DXF_GRID) && (s.pp = plan_pp<1>(a)).variant) s.body = DX_PP;
+  else s.body = DX_IGEMM;
+  return s;
+}
+
+// dW of the stand-alone weight gradient (the one-call backward's shared launches bring their own: bwd_impl)
+enum DwBody { DW_PP, DW_C3X3, DW_STEM, DW_TR };
+static DwBody select_dw(const RiglConvDesc* d) {
+  // (pp_wgrad_legal: cin % 256 == 0, so the knob takes no tiny- / small-Cin layer and, c3x3_legal being 64 -> 64, no c3x3
+  // layer: a c3x3 layer's weight gradient is the c3x3 one from every entry point)
+  if (RIGL_TUNE("pp_wgrad", -1) > 0 && pp_wgrad_legal(d)) return DW_PP;
+  if (c3x3_use(d)) return DW_C3X3;      // X patch and dY tile resident in LDS, nine taps per wave (c3x3.hpp), one slab per workgroup
+  // the ImageNet stem: patch and dY tile resident in LDS, both operands by transposing reads (stem.hpp)
+  if (tiny_cin(d) && stem_direct_legal(d) && RIGL_TUNE("stem_wgrad", 1) != 0) return DW_STEM;
+  return DW_TR;                         // the transpose-read body, over the repacked input of a tiny- / small-Cin layer
+}
 
 }  // namespace k1
 }  // namespace rigl
@@ -1485,32 +1628,17 @@ size_t rigl_conv2d_workspace_bytes(const RiglConvDesc* d, int32_t which) {
   using namespace rigl;
   using namespace rigl::k1;
   if (!d) return 0;
-  const int64_t M = (int64_t)d->n * d->ho * d->wo;
-  if (tiny_cin(d)) {
-    const TinyGeom tg = tiny_geom(d);
-    const size_t xp = align_up((size_t)d->n * tg.hp * tg.wp * 4 * 2, 256);
-    if (which == 0) return xp + align_up((size_t)d->cout * d->kh * tg.cred * 2, 256);
-    if (which == 2) {
-      WgradPlan p = tiny_wgrad_plan((int)M, tg.cred, d->cout, d->kh);
-      const size_t generic = xp + align_up((size_t)p.slab * 4, 256) + align_up((size_t)p.splits * p.slab * 4, 256);
-      const size_t direct = stem_wgrad_workspace(d);       // stem.hpp: no padded copy, one slab per workgroup
-      return generic > direct ? generic : direct;
-    }
-    return 0;
-  }
-  if (small_cin(d)) {
-    const int Kp = kpad(d);
-    size_t col = align_up((size_t)M * Kp * 2, 256);
-    if (which == 0) return col + align_up((size_t)d->cout * Kp * 2, 256);
-    if (which == 2) {
-      WgradPlan p = plan_wgrad((int)M, Kp, d->cout, 1);
-      return col + align_up((size_t)p.splits * p.slab * 4, 256);
-    }
-    return 0;
+  if (tiny_cin(d) || small_cin(d)) {
+    const Repack r = repack_layout(d);
+    if (which == 0) return r.rest + align_up(r.w_bytes, 256);
+    if (which != 2) return 0;
+    const size_t generic = r.rest + r.tmp_bytes + align_up((size_t)r.wg.splits * r.wg.slab * 4, 256);
+    const size_t direct = stem_wgrad_workspace(d);       // stem.hpp: no padded copy, one slab per workgroup (0: not that stem)
+    return generic > direct ? generic : direct;
   }
   if (which == 0) return pp_ksplit_workspace(d);     // the K-split partial tiles of the few-tile forwards (else 0)
   if (which == 2) {
-    WgradPlan p = plan_wgrad((int)M, d->cin, d->cout, d->kh * d->kw);
+    WgradPlan p = plan_wgrad(d->n * d->ho * d->wo, d->cin, d->cout, d->kh * d->kw);
     size_t need = p.splits > 1 ? align_up((size_t)p.splits * p.slab * 4, 256) : 0;
     const size_t npp = align_up(pp_wgrad_workspace(d), 256);   // the ping-pong weight gradients have their own split plans
     if (npp > need) need = npp;
@@ -1526,12 +1654,9 @@ size_t rigl_conv2d_workspace_bytes(const RiglConvDesc* d, int32_t which) {
 }
 
 int32_t rigl_conv2d_stats_parts(const RiglConvDesc* d) {
-  if (!d || d->cout <= 0 || (d->cout % 8)) return 0;
-  const int64_t M = (int64_t)d->n * d->ho * d->wo;
   using namespace rigl::k1;
-  if (c3x3_use(d)) return c3x3_stats_parts(d);     // c3x3.hpp: one partial per (persistent) workgroup
-  { RsPlan rp; if (rs_use<0>(d, &rp)) return rp.gprime; }   // rowstream.hpp: one partial per workgroup of a column slice
-  return (int32_t)((M + 127) / 128);     // one partial per 128-row output tile
+  if (!d || d->cout <= 0 || (d->cout % 8)) return 0;
+  return fwd_stats_parts(d, select_fwd(d, fwd_args(d, nullptr, nullptr, nullptr, nullptr)));
 }
 
 }  // extern "C"
@@ -1545,21 +1670,92 @@ namespace k1 {
 // layer (the stand-alone passes everywhere: the A/B switch).
 static bool relu_fwd_fusable(const RiglConvDesc* d) {
   if (RIGL_TUNE("relu_fuse", 1) == 0 || (d->cout % 8)) return false;
-  if (tiny_cin(d)) return !stem_direct_legal(d);
-  if (small_cin(d)) return true;
-  return !rs_use<0>(d) && !c3x3_use(d);
+  const FwdBody b = select_fwd(d, fwd_args(d, nullptr, nullptr, nullptr, nullptr)).body;
+  return b != FWD_STEM && b != FWD_RS && b != FWD_C3X3;
 }
 // ... and the dgrad body of its one-call backward (the shared igemm / ping-pong launches, or the stand-alone igemm /
 // ping-pong dgrad behind a separate weight gradient)
 static bool relu_dgrad_fusable(const RiglConvDesc* d) {
   if (RIGL_TUNE("relu_fuse", 1) == 0 || (d->cin % 8) || (d->cout % 8)) return false;
-  return !bwd1x1_kind(d) && !bs_use(d) && !rs_use<1>(d) && !c3x3_use(d);
+  const DxBody b = select_dx(d, dgrad_args(d, nullptr, nullptr, nullptr, nullptr)).body;
+  return b == DX_PP || b == DX_IGEMM;
 }
 }  // namespace k1
 }  // namespace rigl
 
 static int fwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* w_ohwi, rigl_bf16* y, float* stats,
-                    size_t stats_floats, void* workspace, size_t workspace_bytes, rigl_stream_t stream, int epi);
+                    size_t stats_floats, void* workspace, size_t workspace_bytes, rigl_stream_t stream, int epi) {
+  using namespace rigl;
+  using namespace rigl::k1;
+  int rc = check_desc(d, "rigl_masked_conv2d_fwd");
+  if (rc) return rc;
+  if (!x || !w_ohwi || !y) return fail(RIGL_EINVAL, "rigl_masked_conv2d_fwd: NULL tensor");
+  if (d->cout % 8) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_fwd: cout %% 8 != 0 (use the reference kernel)");
+  IgemmArgs a = fwd_args(d, x, w_ohwi, y, stats);
+  const FwdSel s = select_fwd(d, a);
+  if (stats && stats_floats < (size_t)fwd_stats_parts(d, s) * 2 * d->cout)
+    return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_fwd_stats: stats buffer %zu floats < %zu", stats_floats,
+                (size_t)fwd_stats_parts(d, s) * 2 * d->cout);
+  hipStream_t st = as_stream(stream);
+  prof_set_tag(d);
+  ProfFamily prof(PROF_CONV_FWD);
+  // The tiny- / small-Cin layers need their workspace: the repacked input, then the repacked filter.  (The ordinary
+  // layers' only workspace is the optional K-split scratch: without it they run unsplit.)
+  Repack r = {};
+  uint16_t *in = nullptr, *wp = nullptr;
+  if (tiny_cin(d) || small_cin(d)) {
+    r = repack_layout(d);
+    if ((rc = check_workspace("rigl_masked_conv2d_fwd", r.rest + align_up(r.w_bytes, 256), workspace, workspace_bytes))) return rc;
+    in = static_cast<uint16_t*>(workspace);
+    wp = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + r.rest);
+    a.A = in; a.a_bytes = (uint32_t)r.in_bytes; a.B = wp; a.b_bytes = (uint32_t)r.w_bytes; a.ph = a.pw = 0;
+  }
+  bool launched = true;
+  switch (s.body) {
+    case FWD_STEM:
+      RIGL_K_LAUNCH(k_stem_weights_shift, dim3(56), dim3(THREADS), 0, st, w_ohwi, wp, d->cout);
+      if (launch_stem_fwd(d, x, wp, y, stats, st)) break;
+      [[fallthrough]];                         // (the kernel did not get its LDS: the padded copy)
+    case FWD_TINY: {
+      PadArgs pa = {x, in, d->n, d->h, d->w, d->cin, r.tg.hp, r.tg.wp, d->pad_top, d->pad_left};
+      RIGL_K_LAUNCH(k_pad_input4, dim3(2048), dim3(THREADS), 0, st, pa);
+      RIGL_K_LAUNCH(k_stem_weights, dim3(64), dim3(THREADS), 0, st, w_ohwi, wp, d->cout, d->kh, d->kw, d->cin, r.tg.cred);
+      a.Cred = r.tg.cred; a.a_pix_stride = 4; a.KW = 1; a.GH = r.tg.hp; a.GW = r.tg.wp;
+      a.b_row_stride = d->kh * r.tg.cred; a.b_tap_stride = r.tg.cred;
+      launched = false;
+      break;
+    }
+    case FWD_IM2COL: {
+      const int K = d->kh * d->kw * d->cin, Kp = kpad(d);
+      Im2colArgs ia = {x, in, a.M, d->cin, d->kh, d->kw, d->h, d->w, d->ho, d->wo, d->stride_h, d->stride_w, d->pad_top, d->pad_left, K, Kp};
+      RIGL_K_LAUNCH(k_im2col, dim3(2048), dim3(THREADS), 0, st, ia);
+      RIGL_K_LAUNCH(k_pad_rows, dim3(64), dim3(THREADS), 0, st, w_ohwi, wp, d->cout, K, Kp);
+      // row space = one long row of M pixels in a single "image"
+      a.Cred = Kp; a.a_pix_stride = Kp; a.KH = a.KW = 1; a.RH = 1; a.RW = a.M; a.GH = 1; a.GW = a.M;
+      a.sh = a.sw = 1; a.b_row_stride = Kp; a.b_tap_stride = 0;
+      launched = false;
+      break;
+    }
+    case FWD_RS: launch_rs<0>(d, s.rs, x, w_ohwi, nullptr, y, stats, st); break;
+    case FWD_C3X3: launch_c3x3<false>(d, x, w_ohwi, nullptr, y, stats, st); break;
+    case FWD_PP:
+      if (pp_ksplit_ok(a, s.pp) && workspace && workspace_bytes >= pp_ksplit_bytes(s.pp)) {
+        a.ksplit = 2;
+        a.KS_SLAB = static_cast<float*>(workspace);
+        a.KS_CNT = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + (size_t)s.pp.grid * 2 * s.pp.bm * s.pp.bn * 4);
+        RIGL_HIP(hipMemsetAsync(a.KS_CNT, 0, (size_t)s.pp.grid * 4, st));
+      }
+      launched = epi == EPI_RELU ? launch_pp<0, EPI_RELU>(s.pp, a, st) : launch_pp<0>(s.pp, a, st);
+      break;
+    case FWD_IGEMM: launched = false; break;
+  }
+  if (!launched) {
+    if (epi == EPI_RELU) launch_igemm<0, false, EPI_RELU>(a, st);
+    else launch_igemm<0, false>(a, st);
+  }
+  RIGL_CHECK_LAUNCH("rigl_masked_conv2d_fwd");
+  return RIGL_OK;
+}
 
 extern "C" {
 
@@ -1588,98 +1784,6 @@ int rigl_masked_conv2d_fwd_relu(const RiglConvDesc* d, const rigl_bf16* x, const
   if (rc) return rc;
   return relu_fwd_launch((int64_t)d->n * d->ho * d->wo * d->cout, y, y, as_stream(stream));
 }
-
-}  // extern "C"
-
-static int fwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* w_ohwi, rigl_bf16* y, float* stats,
-                    size_t stats_floats, void* workspace, size_t workspace_bytes, rigl_stream_t stream, int epi) {
-  using namespace rigl;
-  using namespace rigl::k1;
-  int rc = check_desc(d, "rigl_masked_conv2d_fwd");
-  if (rc) return rc;
-  if (!x || !w_ohwi || !y) return fail(RIGL_EINVAL, "rigl_masked_conv2d_fwd: NULL tensor");
-  if (d->cout % 8) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_fwd: cout %% 8 != 0 (use the reference kernel)");
-  if (stats && stats_floats < (size_t)rigl_conv2d_stats_parts(d) * 2 * d->cout)
-    return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_fwd_stats: stats buffer %zu floats < %zu", stats_floats,
-                (size_t)rigl_conv2d_stats_parts(d) * 2 * d->cout);
-  hipStream_t st = as_stream(stream);
-  prof_set_tag(d);
-  ProfFamily prof(PROF_CONV_FWD);
-  IgemmArgs a = {};
-  a.C = y; a.M = d->n * d->ho * d->wo; a.N = d->cout; a.ldc = d->cout; a.STATS = stats;
-  const size_t need = rigl_conv2d_workspace_bytes(d, 0);
-  // (the ordinary layers' only workspace is the optional K-split scratch: without it they run unsplit)
-  if ((tiny_cin(d) || small_cin(d)) && need && (!workspace || workspace_bytes < need))
-    return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_fwd: workspace %zu < %zu", workspace_bytes, need);
-  if (tiny_cin(d)) {
-    const TinyGeom tg = tiny_geom(d);
-    const size_t xp_bytes = (size_t)d->n * tg.hp * tg.wp * 4 * 2;
-    uint16_t* xp = static_cast<uint16_t*>(workspace);
-    uint16_t* wp = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + align_up(xp_bytes, 256));
-    if (stem_direct_legal(d)) {
-      // the ImageNet stem: the image patch of a 16 x 16 output tile resident in LDS, no padded copy (stem.hpp)
-      RIGL_K_LAUNCH(k_stem_weights_shift, dim3(56), dim3(THREADS), 0, st, w_ohwi, wp, d->cout);
-      if (launch_stem_fwd(d, x, wp, y, stats, st)) {
-        RIGL_CHECK_LAUNCH("rigl_masked_conv2d_fwd");
-        return RIGL_OK;
-      }
-    }
-    PadArgs pa = {x, xp, d->n, d->h, d->w, d->cin, tg.hp, tg.wp, d->pad_top, d->pad_left};
-    RIGL_K_LAUNCH(k_pad_input4, dim3(2048), dim3(THREADS), 0, st, pa);
-    RIGL_K_LAUNCH(k_stem_weights, dim3(64), dim3(THREADS), 0, st, w_ohwi, wp, d->cout, d->kh, d->kw, d->cin, tg.cred);
-    a.A = xp; a.B = wp; a.Cred = tg.cred; a.a_pix_stride = 4; a.KH = d->kh; a.KW = 1; a.RH = d->ho; a.RW = d->wo;
-    a.GH = tg.hp; a.GW = tg.wp; a.sh = d->stride_h; a.sw = d->stride_w; a.ph = a.pw = 0;
-    a.b_row_stride = d->kh * tg.cred; a.b_tap_stride = tg.cred;
-    a.a_bytes = (uint32_t)xp_bytes; a.b_bytes = (uint32_t)((size_t)d->cout * d->kh * tg.cred * 2);
-  } else if (small_cin(d)) {
-    const int K = d->kh * d->kw * d->cin, Kp = kpad(d);
-    uint16_t* col = static_cast<uint16_t*>(workspace);
-    uint16_t* wp = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + align_up((size_t)a.M * Kp * 2, 256));
-    Im2colArgs ia = {x, col, a.M, d->cin, d->kh, d->kw, d->h, d->w, d->ho, d->wo, d->stride_h, d->stride_w, d->pad_top, d->pad_left, K, Kp};
-    RIGL_K_LAUNCH(k_im2col, dim3(2048), dim3(THREADS), 0, st, ia);
-    RIGL_K_LAUNCH(k_pad_rows, dim3(64), dim3(THREADS), 0, st, w_ohwi, wp, d->cout, K, Kp);
-    // row space = one long row of M pixels in a single "image"
-    a.A = col; a.B = wp; a.Cred = Kp; a.a_pix_stride = Kp; a.KH = a.KW = 1; a.RH = 1; a.RW = a.M; a.GH = 1; a.GW = a.M;
-    a.sh = a.sw = 1; a.ph = a.pw = 0; a.b_row_stride = Kp; a.b_tap_stride = 0;
-    a.a_bytes = (uint32_t)((size_t)a.M * Kp * 2); a.b_bytes = (uint32_t)((size_t)d->cout * Kp * 2);
-  } else {
-    a.A = x; a.B = w_ohwi; a.Cred = d->cin; a.a_pix_stride = d->cin; a.KH = d->kh; a.KW = d->kw; a.RH = d->ho; a.RW = d->wo;
-    a.GH = d->h; a.GW = d->w; a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_top; a.pw = d->pad_left;
-    a.b_row_stride = d->kh * d->kw * d->cin; a.b_tap_stride = d->cin;
-    a.a_bytes = (uint32_t)((size_t)d->n * d->h * d->w * d->cin * 2);
-    a.b_bytes = (uint32_t)((size_t)d->kh * d->kw * d->cin * d->cout * 2);
-    {
-      RsPlan rp;
-      if (rs_use<0>(d, &rp)) {                 // 1x1 / stride 1: rows streamed through registers against an LDS-stationary filter slice
-        launch_rs<0>(d, rp, x, w_ohwi, nullptr, y, stats, st);
-        RIGL_CHECK_LAUNCH("rigl_masked_conv2d_fwd");
-        return RIGL_OK;
-      }
-    }
-    if (c3x3_use(d)) {                         // 3x3, 64 -> 64: input patch resident in LDS, filter in registers (c3x3.hpp)
-      launch_c3x3<false>(d, x, w_ohwi, nullptr, y, stats, st);
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_fwd");
-      return RIGL_OK;
-    }
-    const PPPlan pp = plan_pp<0>(a);           // long reductions: the 8-wave ping-pong body
-    if (pp.variant && pp_ksplit_ok(a, pp) && workspace && workspace_bytes >= need && need) {
-      a.ksplit = 2;
-      a.KS_SLAB = static_cast<float*>(workspace);
-      a.KS_CNT = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + (size_t)pp.grid * 2 * pp.bm * pp.bn * 4);
-      RIGL_HIP(hipMemsetAsync(a.KS_CNT, 0, (size_t)pp.grid * 4, st));
-    }
-    if (pp.variant && (epi == EPI_RELU ? launch_pp<0, EPI_RELU>(pp, a, st) : launch_pp<0>(pp, a, st))) {
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_fwd");
-      return RIGL_OK;
-    }
-  }
-  if (epi == EPI_RELU) launch_igemm<0, false, EPI_RELU>(a, st);
-  else launch_igemm<0, false>(a, st);
-  RIGL_CHECK_LAUNCH("rigl_masked_conv2d_fwd");
-  return RIGL_OK;
-}
-
-extern "C" {
 
 // y = conv(relu(bn(x_pre)), w) with the apply pass of the batch norm done on the operand load (rowstream.hpp, BNL kernels):
 // scale_shift = [2][cin] fp32 (rows 2-3 of the batch norm's `saved`), a_out = the activated tensor, written as a side output.
@@ -1749,19 +1853,6 @@ int rigl_masked_conv2d_fwd(const RiglConvDesc* d, const rigl_bf16* x, const rigl
   return rigl_masked_conv2d_fwd_stats(d, x, w_ohwi, y, nullptr, 0, workspace, workspace_bytes, stream);
 }
 
-static rigl::k1::IgemmArgs dgrad_args(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio,
-                                      const rigl_bf16* addend, rigl_bf16* dx) {
-  rigl::k1::IgemmArgs a = {};
-  a.A = dy; a.B = w_hwio; a.C = dx; a.ADD = addend;
-  a.M = d->n * d->h * d->w; a.N = d->cin; a.Cred = d->cout; a.ldc = d->cin;
-  a.KH = d->kh; a.KW = d->kw; a.RH = d->h; a.RW = d->w; a.GH = d->ho; a.GW = d->wo;
-  a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_top; a.pw = d->pad_left;
-  a.b_row_stride = d->cout; a.b_tap_stride = d->cin * d->cout; a.a_pix_stride = d->cout;
-  a.a_bytes = (uint32_t)((size_t)d->n * d->ho * d->wo * d->cout * 2);
-  a.b_bytes = (uint32_t)((size_t)d->kh * d->kw * d->cin * d->cout * 2);
-  return a;
-}
-
 // Which dgrad kernel a layer gets decides whether its epilogue can carry the batch-norm backward reductions: only
 // the igemm body does (the default for every cin % 8 == cout % 8 == 0 layer); returns its number of row tiles, else 0.
 int32_t rigl_conv2d_dgrad_stats_parts(const RiglConvDesc* d) {
@@ -1769,12 +1860,8 @@ int32_t rigl_conv2d_dgrad_stats_parts(const RiglConvDesc* d) {
   using namespace rigl::k1;
   if (!d || check_desc(d, "rigl_conv2d_dgrad_stats_parts")) return 0;
   if ((d->cin % 8) || (d->cout % 8)) return 0;
-  if (bwd1x1_kind(d)) return 0;               // the single-pass 1x1 backward has no reduction epilogue
-  if (bs_use(d)) return 0;                    // nor has its channel-sliced form
-  if (c3x3_use(d)) return 0;                  // nor has the slab-resident 3x3 dgrad
-  if (rs_use<1>(d)) return 0;                 // nor the row-streaming dgrad
   IgemmArgs a = dgrad_args(d, nullptr, nullptr, nullptr, nullptr);
-  if (plan_pp<1>(a).variant) return 0;        // the ping-pong dgrad has no reduction epilogue
+  if (select_dx(d, a).body != DX_IGEMM) return 0;     // the single-pass, row-streaming, c3x3 and ping-pong dgrads have no reduction epilogue
   const IgemmPlan pl = plan_igemm<1>(a);
   return (int32_t)(pl.grid / (unsigned)a.tiles_n);
 }
@@ -1804,7 +1891,43 @@ static void set_addend_sub(rigl::k1::IgemmArgs& a, const RiglConvDesc* d, Addend
 // gates dX in the igemm / ping-pong dgrad epilogue
 static int dgrad_impl(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio, const rigl_bf16* addend,
                       rigl_bf16* dx, const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub = {1, 1},
-                      int epi = rigl::k1::EPI_NONE);
+                      int epi = rigl::k1::EPI_NONE) {
+  using namespace rigl;
+  using namespace rigl::k1;
+  const char* who = "rigl_masked_conv2d_dgrad";
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  if (!dy || !w_hwio || !dx) return fail(RIGL_EINVAL, "rigl_masked_conv2d_dgrad: NULL tensor");
+  if ((d->cin % 8) || (d->cout % 8)) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_dgrad: cin/cout %% 8 != 0 (use the reference kernel)");
+  hipStream_t st = as_stream(stream);
+  prof_set_tag(d);
+  ProfFamily prof(PROF_CONV_DGRAD);
+  const bool subadd = addend_is_sub(addend, sub);
+  if (subadd && bn) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_dgrad: a subsampled addend and the batch-norm reductions do not combine");
+  IgemmArgs a = dgrad_args(d, dy, w_hwio, addend, dx);
+  if (subadd) set_addend_sub(a, d, sub);
+  rc = attach_bn(a, d, bn);
+  if (rc) return rc;
+  const DxForm form = bn || subadd ? DXF_IGEMM : DXF_PLAIN;
+  DxSel s = select_dx(d, a, form);
+  // the big-M 1x1 layers: dX from the single-pass backward kernel (without its weight-gradient half), so that it has the
+  // bits rigl_masked_conv2d_bwd gives it
+  if (s.body == DX_BWD1X1 && !launch_bwd1x1(d, nullptr, dy, w_hwio, addend, dx, nullptr, st)) s = select_dx(d, a, form, true);
+  switch (s.body) {
+    case DX_BWD1X1: case DX_NONE: break;
+    case DX_BS: launch_bs(d, s.bs, nullptr, dy, w_hwio, addend, dx, nullptr, st); break;   // dX half only
+    case DX_RS: launch_rs<1>(d, s.rs, dy, w_hwio, addend, dx, nullptr, st); break;
+    case DX_C3X3: launch_c3x3<true>(d, dy, w_hwio, addend, dx, nullptr, st); break;
+    case DX_PP:
+      if (epi == EPI_RELU ? launch_pp<1, EPI_RELU>(s.pp, a, st) : launch_pp<1>(s.pp, a, st)) break;
+      [[fallthrough]];
+    case DX_IGEMM:
+      if (epi == EPI_RELU) launch_igemm<1, false, EPI_RELU>(a, st);
+      else launch_igemm<1, false>(a, st);
+  }
+  RIGL_CHECK_LAUNCH(who);
+  return RIGL_OK;
+}
 
 int rigl_masked_conv2d_dgrad_acc(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio,
                                  const rigl_bf16* addend, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
@@ -1813,181 +1936,213 @@ int rigl_masked_conv2d_dgrad_acc(const RiglConvDesc* d, const rigl_bf16* dy, con
   return dgrad_impl(d, dy, w_hwio, addend, dx, nullptr, stream);
 }
 
-static int dgrad_impl(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio, const rigl_bf16* addend,
-                      rigl_bf16* dx, const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub, int epi) {
-  using namespace rigl;
-  using namespace rigl::k1;
-  int rc = check_desc(d, "rigl_masked_conv2d_dgrad");
-  if (rc) return rc;
-  if (!dy || !w_hwio || !dx) return fail(RIGL_EINVAL, "rigl_masked_conv2d_dgrad: NULL tensor");
-  if ((d->cin % 8) || (d->cout % 8)) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_dgrad: cin/cout %% 8 != 0 (use the reference kernel)");
-  hipStream_t st = as_stream(stream);
-  prof_set_tag(d);
-  ProfFamily prof(PROF_CONV_DGRAD);
-  if (addend_is_sub(addend, sub)) {
-    if (bn) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_dgrad: a subsampled addend and the batch-norm reductions do not combine");
-    IgemmArgs a = dgrad_args(d, dy, w_hwio, addend, dx);
-    set_addend_sub(a, d, sub);
-    launch_igemm<1, false>(a, st);
-    RIGL_CHECK_LAUNCH("rigl_masked_conv2d_dgrad");
-    return RIGL_OK;
-  }
-  // (the single-pass kernels first, in the order of bwd_impl: a layer's dX has the same bits from both entry points)
-  if (!bn && bwd1x1_kind(d)) {
-    // the big-M 1x1 layers: dX from the single-pass backward kernel (without its weight-gradient half), so that it has
-    // the bits rigl_masked_conv2d_bwd gives it
-    if (launch_bwd1x1(d, nullptr, dy, w_hwio, addend, dx, nullptr, st)) {
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_dgrad");
-      return RIGL_OK;
-    }
-  }
-  {
-    BsPlan bp;
-    if (!bn && bs_use(d, &bp)) {                // the many-input-channel 1x1 layers: the channel-sliced single-pass kernel, dX half only
-      launch_bs(d, bp, nullptr, dy, w_hwio, addend, dx, nullptr, st);
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_dgrad");
-      return RIGL_OK;
-    }
-  }
-  {
-    RsPlan rp;
-    if (!bn && rs_use<1>(d, &rp)) {             // dX[M][cin] = dY[M][cout] x W[cin][cout]^T, rows streamed (rowstream.hpp)
-      launch_rs<1>(d, rp, dy, w_hwio, addend, dx, nullptr, st);
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_dgrad");
-      return RIGL_OK;
-    }
-  }
-  if (!bn && c3x3_use(d)) {
-    launch_c3x3<true>(d, dy, w_hwio, addend, dx, nullptr, st);
-    RIGL_CHECK_LAUNCH("rigl_masked_conv2d_dgrad");
-    return RIGL_OK;
-  }
-  IgemmArgs a = dgrad_args(d, dy, w_hwio, addend, dx);
-  rc = attach_bn(a, d, bn);
-  if (rc) return rc;
-  const PPPlan pp = plan_pp<1>(a);
-  if (pp.variant && (epi == EPI_RELU ? launch_pp<1, EPI_RELU>(pp, a, st) : launch_pp<1>(pp, a, st))) {
-    RIGL_CHECK_LAUNCH("rigl_masked_conv2d_dgrad");
-    return RIGL_OK;
-  }
-  if (epi == EPI_RELU) launch_igemm<1, false, EPI_RELU>(a, st);
-  else launch_igemm<1, false>(a, st);
-  RIGL_CHECK_LAUNCH("rigl_masked_conv2d_dgrad");
-  return RIGL_OK;
-}
-
 int rigl_masked_conv2d_dgrad(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio, rigl_bf16* dx,
                              void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
   return rigl_masked_conv2d_dgrad_acc(d, dy, w_hwio, nullptr, dx, workspace, workspace_bytes, stream);
 }
 
-int rigl_masked_conv2d_wgrad(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, float* dw,
-                             void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
+// The stand-alone weight gradient; `family` is the profiling family its launches are charged to (the c3x3 branch of the
+// one-call backward runs it as part of PROF_CONV_BWD).
+static int wgrad_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, float* dw, void* workspace,
+                      size_t workspace_bytes, rigl_stream_t stream, int family) {
   using namespace rigl;
   using namespace rigl::k1;
-  int rc = check_desc(d, "rigl_masked_conv2d_wgrad");
+  const char* who = "rigl_masked_conv2d_wgrad";
+  int rc = check_desc(d, who);
   if (rc) return rc;
   if (!x || !dy || !dw) return fail(RIGL_EINVAL, "rigl_masked_conv2d_wgrad: NULL tensor");
   if (d->cout % 8) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_wgrad: cout %% 8 != 0 (use the reference kernel)");
   hipStream_t st = as_stream(stream);
-  const size_t need = rigl_conv2d_workspace_bytes(d, 2);
-  if (need && (!workspace || workspace_bytes < need)) return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_wgrad: workspace %zu < %zu", workspace_bytes, need);
+  if ((rc = check_workspace(who, rigl_conv2d_workspace_bytes(d, 2), workspace, workspace_bytes))) return rc;
   prof_set_tag(d);
-  ProfFamily prof(PROF_CONV_WGRAD);
-  if (RIGL_TUNE("pp_wgrad", -1) > 0 && !tiny_cin(d) && !small_cin(d) && pp_wgrad_legal(d)) {
-    const PPBwdPlan pw = plan_wgrad_pp(d, 0u, 0);
-    const WgradArgs aw = pp_wgrad_args(d, x, dy, pw, dw, workspace);
-    if (pp_wgrad_launch(pw, aw, st)) {
-      if (pw.splits > 1) {
-        ReduceArgs ra = {static_cast<const float*>(workspace), dw, pw.slab, pw.slab, pw.splits};
-        launch_wgrad_reduce(ra, st);
+  ProfFamily prof(family);
+  switch (select_dw(d)) {
+    case DW_PP: {
+      const PPBwdPlan pw = plan_wgrad_pp(d, 0u, 0);
+      const WgradArgs aw = pp_wgrad_args(d, x, dy, pw, dw, workspace);
+      if (pp_wgrad_launch(pw, aw, st)) return reduce_dw(who, aw.OUT, dw, pw.slab, pw.slab, pw.splits, st);
+      break;
+    }
+    case DW_C3X3: {
+      float* slabs = static_cast<float*>(workspace);
+      launch_c3x3_wgrad(d, x, dy, slabs, st);
+      return reduce_dw(who, slabs, dw, (int64_t)9 * 64 * 64, (int64_t)9 * 64 * 64, c3x3_wgrad_geom(d).grid, st);
+    }
+    case DW_STEM: {
+      float* tmp = static_cast<float*>(workspace);      // the reduced [7][32][64] image, then one slab per workgroup
+      float* slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)7 * 32 * 64 * 4, 256));
+      if (launch_stem_wgrad(d, x, dy, slabs, st)) {
+        launch_wgrad_reduce({slabs, tmp, (int64_t)7 * 32 * 64, (int64_t)7 * 32 * 64, stem_wgrad_grid(d)}, st);
+        RIGL_K_LAUNCH(k_stem_unpack, dim3(64), dim3(THREADS), 0, st, tmp, dw, 7, 7, 3, 32, 64, 1);
+        RIGL_CHECK_LAUNCH(who);
+        return RIGL_OK;
       }
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_wgrad");
-      return RIGL_OK;
+      break;
     }
+    case DW_TR: break;
   }
-  if (c3x3_use(d)) {
-    // 3x3, 64 -> 64: X patch and dY tile resident in LDS, nine taps per wave (c3x3.hpp), one slab per workgroup
-    float* slabs = static_cast<float*>(workspace);
-    launch_c3x3_wgrad(d, x, dy, slabs, st);
-    ReduceArgs ra = {slabs, dw, (int64_t)9 * 64 * 64, (int64_t)9 * 64 * 64, c3x3_wgrad_geom(d).grid};
-    launch_wgrad_reduce(ra, st);
-    RIGL_CHECK_LAUNCH("rigl_masked_conv2d_wgrad");
-    return RIGL_OK;
-  }
-  if (tiny_cin(d) && stem_direct_legal(d) && RIGL_TUNE("stem_wgrad", 1) != 0) {
-    // the ImageNet stem: patch and dY tile resident in LDS, both operands by transposing reads (stem.hpp)
-    float* tmp = static_cast<float*>(workspace);
-    float* slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)7 * 32 * 64 * 4, 256));
-    if (launch_stem_wgrad(d, x, dy, slabs, st)) {
-      ReduceArgs ra = {slabs, tmp, (int64_t)7 * 32 * 64, (int64_t)7 * 32 * 64, stem_wgrad_grid(d)};
-      launch_wgrad_reduce(ra, st);
-      RIGL_K_LAUNCH(k_stem_unpack, dim3(64), dim3(THREADS), 0, st, tmp, dw, 7, 7, 3, 32, 64, 1);
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_wgrad");
-      return RIGL_OK;
-    }
-  }
-  WgradArgs a = {};
-  a.interleave = RIGL_TUNE("wgrad_il", 1);
-  a.DY = dy; a.M = d->n * d->ho * d->wo; a.Cout = d->cout;
-  a.dy_bytes = (uint32_t)((size_t)a.M * d->cout * 2);
-  int64_t n_out;
+  // The transpose-read body (also where a kernel above did not get its LDS)
+  WgradArgs a = wgrad_args(d, x, dy);
+  int64_t n_out = (int64_t)d->kh * d->kw * d->cin * d->cout;
   char* ws = static_cast<char*>(workspace);
   float* tiny_tmp = nullptr;          // [kh][cred][cout] reduced result of the tiny-Cin path
-  TinyGeom tg = {0, 0, 0};
-  if (tiny_cin(d)) {
-    tg = tiny_geom(d);
-    const size_t xp_bytes = (size_t)d->n * tg.hp * tg.wp * 4 * 2;
-    uint16_t* xp = reinterpret_cast<uint16_t*>(ws);
-    ws += align_up(xp_bytes, 256);
-    PadArgs pa = {x, xp, d->n, d->h, d->w, d->cin, tg.hp, tg.wp, d->pad_top, d->pad_left};
-    RIGL_K_LAUNCH(k_pad_input4, dim3(2048), dim3(THREADS), 0, st, pa);
-    a.X = xp; a.Cin = tg.cred; a.x_pix_stride = 4; a.KH = d->kh; a.KW = 1; a.H = tg.hp; a.W = tg.wp;
-    a.Ho = d->ho; a.Wo = d->wo; a.sh = d->stride_h; a.sw = d->stride_w; a.ph = a.pw = 0;
-    a.x_bytes = (uint32_t)xp_bytes;
-    a.fold = tg.cred; a.Cin = d->kh * tg.cred; a.KH = 1;   // [kh][cred] is one channel axis
-    n_out = (int64_t)d->kh * tg.cred * d->cout;
-    tiny_tmp = reinterpret_cast<float*>(ws);
-    ws += align_up((size_t)n_out * 4, 256);
-  } else if (small_cin(d)) {
-    const int K = d->kh * d->kw * d->cin, Kp = kpad(d);
-    uint16_t* col = reinterpret_cast<uint16_t*>(ws);
-    ws += align_up((size_t)a.M * Kp * 2, 256);
-    Im2colArgs ia = {x, col, a.M, d->cin, d->kh, d->kw, d->h, d->w, d->ho, d->wo, d->stride_h, d->stride_w, d->pad_top, d->pad_left, K, Kp};
-    RIGL_K_LAUNCH(k_im2col, dim3(2048), dim3(THREADS), 0, st, ia);
-    a.X = col; a.Cin = Kp; a.x_pix_stride = Kp; a.KH = a.KW = 1; a.H = 1; a.W = a.M; a.Ho = 1; a.Wo = a.M;
-    a.sh = a.sw = 1; a.ph = a.pw = 0;
-    a.x_bytes = (uint32_t)((size_t)a.M * Kp * 2);
-    n_out = (int64_t)K * d->cout;
-  } else {
-    a.X = x; a.Cin = d->cin; a.x_pix_stride = d->cin; a.KH = d->kh; a.KW = d->kw; a.H = d->h; a.W = d->w;
-    a.Ho = d->ho; a.Wo = d->wo; a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_top; a.pw = d->pad_left;
-    a.x_bytes = (uint32_t)((size_t)d->n * d->h * d->w * d->cin * 2);
-    n_out = (int64_t)d->kh * d->kw * d->cin * d->cout;
+  Repack r = {};
+  if (tiny_cin(d) || small_cin(d)) {
+    r = repack_layout(d);
+    a.X = reinterpret_cast<uint16_t*>(ws); a.x_bytes = (uint32_t)r.in_bytes; a.KH = a.KW = 1; a.ph = a.pw = 0;
+    if (tiny_cin(d)) {
+      PadArgs pa = {x, reinterpret_cast<uint16_t*>(ws), d->n, d->h, d->w, d->cin, r.tg.hp, r.tg.wp, d->pad_top, d->pad_left};
+      RIGL_K_LAUNCH(k_pad_input4, dim3(2048), dim3(THREADS), 0, st, pa);
+      a.x_pix_stride = 4; a.H = r.tg.hp; a.W = r.tg.wp;
+      a.fold = r.tg.cred; a.Cin = d->kh * r.tg.cred;     // [kh][cred] is one channel axis
+      n_out = r.wg.slab;
+      tiny_tmp = reinterpret_cast<float*>(ws + r.rest);
+    } else {
+      const int K = d->kh * d->kw * d->cin, Kp = kpad(d);
+      Im2colArgs ia = {x, reinterpret_cast<uint16_t*>(ws), a.M, d->cin, d->kh, d->kw, d->h, d->w, d->ho, d->wo, d->stride_h, d->stride_w, d->pad_top, d->pad_left, K, Kp};
+      RIGL_K_LAUNCH(k_im2col, dim3(2048), dim3(THREADS), 0, st, ia);
+      a.Cin = Kp; a.x_pix_stride = Kp; a.H = 1; a.W = a.M; a.Ho = 1; a.Wo = a.M; a.sh = a.sw = 1;
+      n_out = (int64_t)K * d->cout;
+    }
+    ws += r.rest + r.tmp_bytes;
   }
-  WgradPlan p = plan_wgrad(a.M, a.Cin, a.Cout, a.KH * a.KW);
+  const WgradPlan p = plan_wgrad(a.M, a.Cin, a.Cout, a.KH * a.KW);
   a.tiles_ci = p.tiles_ci; a.tiles_co = p.tiles_co; a.splits = p.splits; a.slab_elems = p.slab;
   const bool two_pass = p.splits > 1 || small_cin(d) || tiny_cin(d);
   a.OUT = two_pass ? reinterpret_cast<float*>(ws) : dw;
-  dim3 grid((unsigned)((int64_t)p.tiles_ci * p.tiles_co * a.KH * a.KW * p.splits)), blk(THREADS);
-  if (wgrad_stages(p.tm, p.tn) == 3) RIGL_K_LAUNCH((k_wgrad_tr<2, 2, 3>), grid, blk, 0, st, a);
-  else if (p.tm == 2) RIGL_K_LAUNCH((k_wgrad_tr<2, 1, 4>), grid, blk, 0, st, a);
-  else if (p.tn == 2) RIGL_K_LAUNCH((k_wgrad_tr<1, 2, 4>), grid, blk, 0, st, a);
-  else RIGL_K_LAUNCH((k_wgrad_tr<1, 1, 4>), grid, blk, 0, st, a);
-  if (two_pass) {
-    ReduceArgs ra = {reinterpret_cast<const float*>(ws), tiny_tmp ? tiny_tmp : dw, n_out, p.slab, p.splits};
-    launch_wgrad_reduce(ra, st);
-  }
-  if (tiny_tmp)
-    RIGL_K_LAUNCH(k_stem_unpack, dim3(64), blk, 0, st, tiny_tmp, dw, d->kh, d->kw, d->cin, tg.cred, d->cout, 0);
-  RIGL_CHECK_LAUNCH("rigl_masked_conv2d_wgrad");
+  const dim3 grid((unsigned)((int64_t)p.tiles_ci * p.tiles_co * a.KH * a.KW * p.splits)), blk(THREADS);
+#define RIGL_TR(TM, TN, ST, KB) RIGL_K_LAUNCH((KB<TM, TN, ST>), grid, blk, 0, st, a);
+  RIGL_WGRAD_TILE(p, RIGL_TR, k_wgrad_tr)
+#undef RIGL_TR
+  if (!tiny_tmp) return reduce_dw(who, a.OUT, dw, n_out, p.slab, p.splits, st);
+  launch_wgrad_reduce({a.OUT, tiny_tmp, n_out, p.slab, p.splits}, st);
+  RIGL_K_LAUNCH(k_stem_unpack, dim3(64), blk, 0, st, tiny_tmp, dw, d->kh, d->kw, d->cin, r.tg.cred, d->cout, 0);
+  RIGL_CHECK_LAUNCH(who);
   return RIGL_OK;
+}
+
+int rigl_masked_conv2d_wgrad(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, float* dw,
+                             void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
+  return wgrad_impl(d, x, dy, dw, workspace, workspace_bytes, stream, rigl::PROF_CONV_WGRAD);
 }
 
 static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
                     const rigl_bf16* addend, float* dw, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
                     const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub = {1, 1},
-                    const RiglConvDesc* dg = nullptr, const uint8_t* addend_bits = nullptr, int epi = rigl::k1::EPI_NONE);
+                    const RiglConvDesc* dg = nullptr, const uint8_t* addend_bits = nullptr, int epi = rigl::k1::EPI_NONE) {
+  // dg (rigl_masked_conv2d_bwd_grid): the dgrad half runs on THIS descriptor -- the stride-1 twin of a strided 1x1 conv
+  // on its own output grid -- while the weight gradient reads x through d; the two halves of the shared launch take
+  // their geometry from separate argument blocks anyway.
+  using namespace rigl;
+  using namespace rigl::k1;
+  static const bool fuse = [] { const char* e = getenv("RIGL_BWD_FUSED"); return e ? atoi(e) != 0 : true; }();
+  const RiglConvDesc* dd = dg ? dg : d;
+  const char* who = "rigl_masked_conv2d_bwd";
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  prof_set_tag(d);
+  const bool subadd = addend_is_sub(addend, sub);
+  if (subadd && bn) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd: a subsampled addend and the batch-norm reductions do not combine");
+  if (subadd && !dx) return fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd: an addend without dX");
+  const size_t need = rigl_conv2d_workspace_bytes(d, 2);
+  float* const slabs = static_cast<float*>(workspace);
+  // Both gradients asked for, every operand there: the bodies that compute dX and dW in one call.  Each checks the
+  // workspace before its first launch.
+  if (dx && x && dy && w_hwio && dw) {
+    const DxForm form = bn ? DXF_IGEMM : subadd ? DXF_SUB : dg ? DXF_GRID : addend_bits ? DXF_MASKED : DXF_PLAIN;
+    IgemmArgs ad = dgrad_args(dd, dy, w_hwio, addend, dx);
+    DxSel s = select_dx(dd, ad, form);
+    if (s.body == DX_BWD1X1) {
+      // dX and dW in ONE pass over dY (bwd1x1.hpp), one slab per workgroup, then the reduce.  bwd1x1_ready is asked
+      // BEFORE committing to the path, so a refused dynamic-LDS opt-in falls through to the generic bodies cleanly.
+      if (bwd1x1_ready(d)) {
+        if ((rc = check_workspace(who, need, workspace, workspace_bytes))) return rc;
+        ProfFamily prof(PROF_CONV_BWD);
+        if (launch_bwd1x1(d, x, dy, w_hwio, addend, dx, slabs, st))
+          return reduce_dw(who, slabs, dw, (int64_t)d->cin * d->cout, (int64_t)d->cin * d->cout, bwd1x1_splits(), st);
+      }
+      s = select_dx(dd, ad, form, true);
+    }
+    switch (s.body) {
+      case DX_BS: {                // one slab per row group
+        if ((rc = check_workspace(who, need, workspace, workspace_bytes))) return rc;
+        ProfFamily prof(PROF_CONV_BWD);
+        launch_bs(d, s.bs, x, dy, w_hwio, addend, dx, slabs, st, sub.sh, sub.sw, addend_bits);
+        return reduce_dw(who, slabs, dw, (int64_t)d->cin * d->cout, (int64_t)d->cin * d->cout, s.bs.G, st);
+      }
+      // Layers whose dgrad streams rows, or runs on c3x3's resident patches: the stand-alone weight gradient, then the
+      // dgrad -- two launches (+ reduce) instead of the shared one.  (The row-streaming branch has always charged its
+      // weight gradient to PROF_CONV_WGRAD and its dgrad to PROF_CONV_BWD, the c3x3 branch everything to PROF_CONV_BWD.)
+      case DX_RS: case DX_C3X3: {
+        rc = wgrad_impl(d, x, dy, dw, workspace, workspace_bytes, stream, s.body == DX_RS ? PROF_CONV_WGRAD : PROF_CONV_BWD);
+        if (rc) return rc;
+        ProfFamily prof(PROF_CONV_BWD);
+        if (s.body == DX_RS) launch_rs<1>(d, s.rs, dy, w_hwio, addend, dx, nullptr, st, addend_bits);
+        else launch_c3x3<true>(d, dy, w_hwio, addend, dx, nullptr, st);
+        RIGL_CHECK_LAUNCH(who);
+        return RIGL_OK;
+      }
+      default: break;
+    }
+    // The shared launch on the 8-wave ping-pong bodies ("pp_bwd"): layers whose weight gradient has 256-channel tiles and
+    // whose dgrad is a long reduction (plan_pp<1> follows pp_bwd_dgrad_variant, which implies pp_wgrad_legal).  A forced
+    // stand-alone dgrad tile ("pp_dgrad" >= 0) wins: that layer runs wgrad and dgrad as two launches.
+    if (s.body == DX_PP && RIGL_TUNE("pp_dgrad", -1) < 0) {
+      IgemmArgs ap = ad;
+      const bool strided = pp_strided(ap);
+      if (strided) pp_fill_classes(ap, s.pp.bm);
+      // dgrad workgroup length in 256x256-tile K-tile units (a parity class visits about taps / (sh * sw) of the taps)
+      const int kt_d = (int)((int64_t)dd->kh * dd->kw * (dd->cout / 64) * s.pp.bm * s.pp.bn / (256 * 256) / (dd->stride_h * dd->stride_w));
+      const PPBwdPlan pw = plan_wgrad_pp(d, s.pp.grid, kt_d);
+      if ((rc = check_workspace(who, need, workspace, workspace_bytes))) return rc;
+      ProfFamily prof(PROF_CONV_BWD);
+      const WgradArgs aw = pp_wgrad_args(d, x, dy, pw, dw, workspace);
+      ap.fd_rw = make_fastdiv(ap.RW); ap.fd_rh = make_fastdiv(ap.RH);
+      ap.tiles_n = ap.N / s.pp.bn;
+      if (epi == EPI_RELU ? pp_bwd_launch<EPI_RELU>(s.pp.variant, strided, ap, aw, pw, st) : pp_bwd_launch(s.pp.variant, strided, ap, aw, pw, st))
+        return reduce_dw(who, aw.OUT, dw, pw.slab, pw.slab, pw.splits, st);
+    }
+    // The shared launch on the igemm / tr bodies (k_bwd_fused).  Not for a layer whose dgrad has a ping-pong plan: that
+    // body accumulates in another order than the igemm body here, so such a layer runs wgrad and dgrad as two launches --
+    // except the own-grid form, which has no stand-alone twin to agree with.
+    if ((s.body == DX_IGEMM || (s.body == DX_PP && dg)) && fuse && (d->cin % 8) == 0 && (d->cout % 8) == 0) {
+      if (subadd) set_addend_sub(ad, dd, sub);
+      rc = attach_bn(ad, d, bn);
+      if (rc) return rc;
+      const IgemmPlan pd = plan_igemm<1>(ad);
+      // (launched alone back to back, a large short-reduction dgrad -- the 56x56 / 28x28 1x1 "reduce" convs -- is 9-28 %
+      // slower when it shares the launch, the other layers 3-10 % faster; inside the training step sharing always won)
+      if (pd.dma) {
+        if ((rc = check_workspace(who, need, workspace, workspace_bytes))) return rc;
+        ProfFamily prof(PROF_CONV_BWD);
+        WgradArgs aw = wgrad_args(d, x, dy);
+        const WgradPlan p = plan_wgrad(aw.M, aw.Cin, aw.Cout, aw.KH * aw.KW, true);
+        aw.tiles_ci = p.tiles_ci; aw.tiles_co = p.tiles_co; aw.splits = p.splits; aw.slab_elems = p.slab;
+        aw.OUT = p.splits > 1 ? slabs : dw;
+        const unsigned nd = pd.grid, nw = (unsigned)((int64_t)p.tiles_ci * p.tiles_co * aw.KH * aw.KW * p.splits);
+        const dim3 grid(nd + nw), blk(THREADS);
+#define RIGL_FUSED_TILE(TM, TN, ST, KB, TND, CLSD) RIGL_K_LAUNCH((KB<TND, CLSD, TM, TN, ST>), grid, blk, 0, st, ad, aw, nd, nw);
+#define RIGL_FUSED(KB, TND, CLSD) RIGL_WGRAD_TILE(p, RIGL_FUSED_TILE, KB, TND, CLSD)
+        if (epi == EPI_RELU) {
+          if (pd.wide_n) { if (pd.cls) RIGL_FUSED(k_bwd_fused_relu, 2, true) else RIGL_FUSED(k_bwd_fused_relu, 2, false) }
+          else { if (pd.cls) RIGL_FUSED(k_bwd_fused_relu, 1, true) else RIGL_FUSED(k_bwd_fused_relu, 1, false) }
+        } else {
+          if (pd.wide_n) { if (pd.cls) RIGL_FUSED(k_bwd_fused, 2, true) else RIGL_FUSED(k_bwd_fused, 2, false) }
+          else { if (pd.cls) RIGL_FUSED(k_bwd_fused, 1, true) else RIGL_FUSED(k_bwd_fused, 1, false) }
+        }
+#undef RIGL_FUSED
+#undef RIGL_FUSED_TILE
+        return reduce_dw(who, aw.OUT, dw, (int64_t)d->kh * d->kw * d->cin * d->cout, p.slab, p.splits, st);
+      }
+    }
+  }
+  if (addend_bits)
+    return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_masked: this layer's kernels take no masked addend (ask rigl_conv2d_bwd_takes_masked_addend)");
+  rc = wgrad_impl(d, x, dy, dw, workspace, workspace_bytes, stream, PROF_CONV_WGRAD);
+  if (rc || !dx) return rc;
+  return dgrad_impl(dd, dy, w_hwio, addend, dx, bn, stream, sub, epi);
+}
 
 // rigl_masked_conv2d_bwd with the batch-norm backward reductions of the tensor dX is the gradient of riding in the dgrad
 // epilogue.
@@ -1996,177 +2151,6 @@ int rigl_masked_conv2d_bwd_bn(const RiglConvDesc* d, const rigl_bf16* x, const r
                               const RiglBnReduceFuse* bn, rigl_stream_t stream) {
   if (bn && !dx) return rigl::fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd_bn: the reductions ride on dX, which was not requested");
   return bwd_impl(d, x, dy, w_hwio, addend, dw, dx, workspace, workspace_bytes, bn, stream);
-}
-
-static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
-                    const rigl_bf16* addend, float* dw, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
-                    const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub, const RiglConvDesc* dg,
-                    const uint8_t* addend_bits, int epi) {
-  // dg (rigl_masked_conv2d_bwd_grid): the dgrad half runs on THIS descriptor -- the stride-1 twin of a strided 1x1 conv
-  // on its own output grid -- while the weight gradient reads x through d; the two halves of the shared launch take
-  // their geometry from separate argument blocks anyway.
-  using namespace rigl;
-  using namespace rigl::k1;
-  static const bool fuse = [] { const char* e = getenv("RIGL_BWD_FUSED"); return e ? atoi(e) != 0 : true; }();
-  const RiglConvDesc* dd = dg ? dg : d;
-  int rc = check_desc(d, "rigl_masked_conv2d_bwd");
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  prof_set_tag(d);
-  const bool subadd = addend_is_sub(addend, sub);          // (only the igemm body's epilogue: the special paths step aside)
-  if (subadd && bn) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd: a subsampled addend and the batch-norm reductions do not combine");
-  if (subadd && !dx) return fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd: an addend without dX");
-  const bool both = dx && x && dy && w_hwio && dw;          // both gradients asked for, every operand there
-  const bool whole = both && !subadd && !dg;                // ... and nothing that keeps the layer off its special kernels
-  const size_t need = rigl_conv2d_workspace_bytes(d, 2);
-  // A layer's dX must come from the same kernel whichever entry point computes it (rigl_masked_conv2d_dgrad or this
-  // one): the ping-pong body accumulates in another order than the igemm body of the shared launch, so layers whose
-  // dgrad has a ping-pong plan run wgrad and dgrad as two launches.
-  bool dgrad_pp = false;
-  if (dx && (d->cin % 8) == 0 && (d->cout % 8) == 0 && !bn && !subadd && !dg) {
-    const IgemmArgs ap = dgrad_args(d, dy, w_hwio, addend, dx);
-    dgrad_pp = plan_pp<1>(ap).variant != 0;
-  }
-  // The big-M 1x1 layers: dX and dW in ONE pass over dY (bwd1x1.hpp), one slab per workgroup, then the reduce
-  if (whole && !bn && !addend_bits && bwd1x1_kind(d) && bwd1x1_ready(d)) {
-    if (need && (!workspace || workspace_bytes < need))
-      return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_bwd: workspace %zu < %zu", workspace_bytes, need);
-    ProfFamily prof(PROF_CONV_BWD);
-    if (launch_bwd1x1(d, x, dy, w_hwio, addend, dx, static_cast<float*>(workspace), st)) {
-      const int64_t n_out = (int64_t)d->cin * d->cout;
-      ReduceArgs ra = {static_cast<const float*>(workspace), dw, n_out, n_out, bwd1x1_splits()};
-      launch_wgrad_reduce(ra, st);
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_bwd");
-      return RIGL_OK;
-    }
-  }
-  // The many-input-channel 1x1 layers: the same single pass per 128-channel slice (bwdslice.hpp), one slab per row group
-  {
-    BsPlan bp;
-    // (a subsampled addend -- the first block of a group -- rides in the same DMA ring: rows without an addend row read zeros)
-    if (both && !dg && !bn && bs_use(d, &bp)) {
-      if (need && (!workspace || workspace_bytes < need))
-        return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_bwd: workspace %zu < %zu", workspace_bytes, need);
-      ProfFamily prof(PROF_CONV_BWD);
-      launch_bs(d, bp, x, dy, w_hwio, addend, dx, static_cast<float*>(workspace), st, sub.sh, sub.sw, addend_bits);
-      const int64_t n_out = (int64_t)d->cin * d->cout;
-      ReduceArgs ra = {static_cast<const float*>(workspace), dw, n_out, n_out, bp.G};
-      launch_wgrad_reduce(ra, st);
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_bwd");
-      return RIGL_OK;
-    }
-  }
-  if (addend_bits && !(whole && rs_masked_use(d)))
-    return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_masked: this layer's kernels take no masked addend (ask rigl_conv2d_bwd_takes_masked_addend)");
-  // Layers whose dgrad streams rows (rowstream.hpp): the weight gradient with its stand-alone plan, then the dgrad -- two
-  // launches (+ reduce) instead of the shared one
-  {
-    RsPlan rp;
-    if (whole && !bn && rs_use<1>(d, &rp)) {
-      ProfFamily prof(PROF_CONV_BWD);
-      rc = rigl_masked_conv2d_wgrad(d, x, dy, dw, workspace, workspace_bytes, stream);
-      if (rc) return rc;
-      prof_current_kind() = PROF_CONV_BWD;
-      launch_rs<1>(d, rp, dy, w_hwio, addend, dx, nullptr, st, addend_bits);
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_bwd");
-      return RIGL_OK;
-    }
-  }
-  // 3x3, 64 -> 64 (c3x3.hpp): weight gradient (+ reduce) and dgrad are launches of their own, each on resident patches
-  if (whole && !bn && c3x3_use(d)) {
-    if (need && (!workspace || workspace_bytes < need))
-      return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_bwd: workspace %zu < %zu", workspace_bytes, need);
-    ProfFamily prof(PROF_CONV_BWD);
-    float* slabs = static_cast<float*>(workspace);
-    launch_c3x3_wgrad(d, x, dy, slabs, st);
-    ReduceArgs ra = {slabs, dw, (int64_t)9 * 64 * 64, (int64_t)9 * 64 * 64, c3x3_wgrad_geom(d).grid};
-    launch_wgrad_reduce(ra, st);
-    launch_c3x3<true>(d, dy, w_hwio, addend, dx, nullptr, st);
-    RIGL_CHECK_LAUNCH("rigl_masked_conv2d_bwd");
-    return RIGL_OK;
-  }
-  // The shared launch on the 8-wave ping-pong bodies ("pp_bwd"): layers whose weight gradient has 256-channel tiles and
-  // whose dgrad is a long reduction.
-  if (RIGL_TUNE("pp_bwd", -1) != 0 && both && !subadd && !bn && !tiny_cin(d) && !small_cin(d) && pp_wgrad_legal(d)) {
-    IgemmArgs ad = dgrad_args(dd, dy, w_hwio, addend, dx);
-    const int dvar = RIGL_TUNE("pp_dgrad", -1) >= 0 ? PP_NONE : pp_bwd_dgrad_variant(ad);   // (a forced stand-alone dgrad tile wins)
-    if (dvar != PP_NONE && pp_legal<1>(ad, dvar)) {
-      int bm, bn2;
-      pp_dims(dvar, bm, bn2);
-      const bool strided = pp_strided(ad);
-      const int tiles_m = strided ? pp_fill_classes(ad, bm) : (ad.M + bm - 1) / bm;
-      const unsigned nd = (unsigned)(tiles_m * (ad.N / bn2));
-      // dgrad workgroup length in 256x256-tile K-tile units (a parity class visits about taps / (sh * sw) of the taps)
-      const int kt_d = (int)((int64_t)dd->kh * dd->kw * (dd->cout / 64) * bm * bn2 / (256 * 256) / (dd->stride_h * dd->stride_w));
-      const PPBwdPlan pw = plan_wgrad_pp(d, nd, kt_d);
-      if (need && (!workspace || workspace_bytes < need))
-        return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_bwd: workspace %zu < %zu", workspace_bytes, need);
-      ProfFamily prof(PROF_CONV_BWD);
-      const WgradArgs aw = pp_wgrad_args(d, x, dy, pw, dw, workspace);
-      ad.fd_rw = make_fastdiv(ad.RW); ad.fd_rh = make_fastdiv(ad.RH);
-      ad.tiles_n = ad.N / bn2;
-      if (epi == EPI_RELU ? pp_bwd_launch<EPI_RELU>(dvar, strided, ad, aw, pw, st) : pp_bwd_launch(dvar, strided, ad, aw, pw, st)) {
-        if (pw.splits > 1) {
-          ReduceArgs ra = {static_cast<const float*>(workspace), dw, pw.slab, pw.slab, pw.splits};
-          launch_wgrad_reduce(ra, st);
-        }
-        RIGL_CHECK_LAUNCH("rigl_masked_conv2d_bwd");
-        return RIGL_OK;
-      }
-    }
-  }
-  if (fuse && !dgrad_pp && both && !tiny_cin(d) && !small_cin(d) && (d->cin % 8) == 0 && (d->cout % 8) == 0) {
-    IgemmArgs ad = dgrad_args(dd, dy, w_hwio, addend, dx);
-    if (subadd) set_addend_sub(ad, dd, sub);
-    rc = attach_bn(ad, d, bn);
-    if (rc) return rc;
-    const IgemmPlan pd = plan_igemm<1>(ad);
-    WgradArgs aw = {};
-    aw.interleave = RIGL_TUNE("wgrad_il", 1);
-    aw.DY = dy; aw.M = d->n * d->ho * d->wo; aw.Cout = d->cout;
-    aw.dy_bytes = (uint32_t)((size_t)aw.M * d->cout * 2);
-    aw.X = x; aw.Cin = d->cin; aw.x_pix_stride = d->cin; aw.KH = d->kh; aw.KW = d->kw; aw.H = d->h; aw.W = d->w;
-    aw.Ho = d->ho; aw.Wo = d->wo; aw.sh = d->stride_h; aw.sw = d->stride_w; aw.ph = d->pad_top; aw.pw = d->pad_left;
-    aw.x_bytes = (uint32_t)((size_t)d->n * d->h * d->w * d->cin * 2);
-    const WgradPlan p = plan_wgrad(aw.M, aw.Cin, aw.Cout, aw.KH * aw.KW, true);
-    // (launched alone back to back, a large short-reduction dgrad -- the 56x56 / 28x28 1x1 "reduce" convs -- is 9-28 %
-    // slower when it shares the launch, the other layers 3-10 % faster; inside the training step sharing always won)
-    if (pd.dma) {
-      if (need && (!workspace || workspace_bytes < need))
-        return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_bwd: workspace %zu < %zu", workspace_bytes, need);
-      ProfFamily prof(PROF_CONV_BWD);
-      aw.tiles_ci = p.tiles_ci; aw.tiles_co = p.tiles_co; aw.splits = p.splits; aw.slab_elems = p.slab;
-      const bool two_pass = p.splits > 1;
-      aw.OUT = two_pass ? static_cast<float*>(workspace) : dw;
-      const unsigned nd = pd.grid, nw = (unsigned)((int64_t)p.tiles_ci * p.tiles_co * aw.KH * aw.KW * p.splits);
-      const dim3 grid(nd + nw), blk(THREADS);
-#define RIGL_FUSED(KB, TND, CLSD)                                                                                      \
-      {                                                                                                                \
-        if (p.tm == 2 && p.tn == 2) RIGL_K_LAUNCH((KB<TND, CLSD, 2, 2, 3>), grid, blk, 0, st, ad, aw, nd, nw);          \
-        else if (p.tm == 2) RIGL_K_LAUNCH((KB<TND, CLSD, 2, 1, 4>), grid, blk, 0, st, ad, aw, nd, nw);                   \
-        else if (p.tn == 2) RIGL_K_LAUNCH((KB<TND, CLSD, 1, 2, 4>), grid, blk, 0, st, ad, aw, nd, nw);                   \
-        else RIGL_K_LAUNCH((KB<TND, CLSD, 1, 1, 4>), grid, blk, 0, st, ad, aw, nd, nw);                                  \
-      }
-      if (epi == EPI_RELU) {
-        if (pd.wide_n) { if (pd.cls) RIGL_FUSED(k_bwd_fused_relu, 2, true) else RIGL_FUSED(k_bwd_fused_relu, 2, false) }
-        else { if (pd.cls) RIGL_FUSED(k_bwd_fused_relu, 1, true) else RIGL_FUSED(k_bwd_fused_relu, 1, false) }
-      } else {
-        if (pd.wide_n) { if (pd.cls) RIGL_FUSED(k_bwd_fused, 2, true) else RIGL_FUSED(k_bwd_fused, 2, false) }
-        else { if (pd.cls) RIGL_FUSED(k_bwd_fused, 1, true) else RIGL_FUSED(k_bwd_fused, 1, false) }
-      }
-#undef RIGL_FUSED
-      if (two_pass) {
-        const int64_t n_out = (int64_t)d->kh * d->kw * d->cin * d->cout;
-        ReduceArgs ra = {static_cast<const float*>(workspace), dw, n_out, p.slab, p.splits};
-        launch_wgrad_reduce(ra, st);
-      }
-      RIGL_CHECK_LAUNCH("rigl_masked_conv2d_bwd");
-      return RIGL_OK;
-    }
-  }
-  rc = rigl_masked_conv2d_wgrad(d, x, dy, dw, workspace, workspace_bytes, stream);
-  if (rc || !dx) return rc;
-  return dgrad_impl(dd, dy, w_hwio, addend, dx, bn, stream, sub, epi);
 }
 
 // Backward of y = relu(conv(x, w)) where x is itself the output of a ReLU (or a max pool of one) and dy arrives already
@@ -2214,13 +2198,17 @@ int32_t rigl_conv2d_bwd_takes_masked_addend(const RiglConvDesc* d) {
   using namespace rigl;
   using namespace rigl::k1;
   if (!d || check_desc(d, "rigl_conv2d_bwd_takes_masked_addend")) return 0;
-  if (bs_use(d)) return 1;
-  // (the order of bwd_impl: a layer the single-pass 1x1 kernel takes never reaches the row-streaming dgrad)
-  if ((bwd1x1_kind(d) && bwd1x1_ready(d)) || !rs_masked_use(d)) return 0;
-  // The row-streaming dgrad: rigl_masked_conv2d_bwd_masked runs wherever the kernel is legal, but a caller that asks here
-  // whether to SKIP writing the masked copy is told yes only from 65 536 rows on (measured at batch 128, 401 408 rows;
-  // below that the graph keeps its former hand-over); knob "rs_masked_addend" = 2: every legal layer.
-  return RIGL_TUNE("rs_masked_addend", 1) == 2 || (int64_t)d->n * d->h * d->w >= 65536 ? 1 : 0;
+  const IgemmArgs a = dgrad_args(d, nullptr, nullptr, nullptr, nullptr);
+  // (a layer whose plain backward the single-pass 1x1 kernel takes is left to it)
+  if (select_dx(d, a).body == DX_BWD1X1 && bwd1x1_ready(d)) return 0;
+  switch (select_dx(d, a, DXF_MASKED).body) {
+    case DX_BS: return 1;
+    // The row-streaming dgrad: rigl_masked_conv2d_bwd_masked runs wherever the kernel is legal, but a caller that asks here
+    // whether to SKIP writing the masked copy is told yes only from 65 536 rows on (measured at batch 128, 401 408 rows;
+    // below that the graph keeps its former hand-over); knob "rs_masked_addend" = 2: every legal layer.
+    case DX_RS: return RIGL_TUNE("rs_masked_addend", 1) == 2 || (int64_t)d->n * d->h * d->w >= 65536 ? 1 : 0;
+    default: return 0;
+  }
 }
 // rigl_masked_conv2d_bwd of the conv IN FRONT of a batch norm whose backward apply pass is not run: `dout` is the gradient w.r.t.
 // relu(bn(y) + shortcut), and the kernel forms dy = bf16(a * (dz - b - xhat * c)) on its operand load from dout, y (this conv's
@@ -2244,19 +2232,14 @@ int rigl_masked_conv2d_bwd_bnapply(const RiglConvDesc* d, const rigl_bf16* x, co
     return fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd_bnapply: NULL tensor");
   if (!bwd1x1_bna_ready(d))
     return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_bnapply: this layer's backward does not take the transform (rigl_conv2d_bwd_takes_bn_apply)");
-  const size_t need = rigl_conv2d_workspace_bytes(d, 2);
-  if (need && (!workspace || workspace_bytes < need))
-    return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_bwd_bnapply: workspace %zu < %zu", workspace_bytes, need);
+  if ((rc = check_workspace("rigl_masked_conv2d_bwd_bnapply", rigl_conv2d_workspace_bytes(d, 2), workspace, workspace_bytes))) return rc;
   hipStream_t st = as_stream(stream);
   prof_set_tag(d);
   ProfFamily prof(PROF_CONV_BWD);
-  if (!launch_bwd1x1_bna(d, x, dout, w_hwio, addend, dx, static_cast<float*>(workspace), y, relu_bits, mean, invstd, coef, st))
+  float* const slabs = static_cast<float*>(workspace);
+  if (!launch_bwd1x1_bna(d, x, dout, w_hwio, addend, dx, slabs, y, relu_bits, mean, invstd, coef, st))
     return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_bnapply: the kernel did not launch");
-  const int64_t n_out = (int64_t)d->cin * d->cout;
-  ReduceArgs ra = {static_cast<const float*>(workspace), dw, n_out, n_out, bwd1x1_splits()};
-  launch_wgrad_reduce(ra, st);
-  RIGL_CHECK_LAUNCH("rigl_masked_conv2d_bwd_bnapply");
-  return RIGL_OK;
+  return reduce_dw("rigl_masked_conv2d_bwd_bnapply", slabs, dw, (int64_t)d->cin * d->cout, (int64_t)d->cin * d->cout, bwd1x1_splits(), st);
 }
 
 int rigl_masked_conv2d_bwd_masked(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,

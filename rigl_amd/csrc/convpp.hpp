@@ -847,14 +847,8 @@ static PPBwdPlan plan_wgrad_pp(const RiglConvDesc* d, unsigned nd, int kt_d) {
 
 static WgradArgs pp_wgrad_args(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const PPBwdPlan& p, float* dw,
                                void* workspace) {
-  WgradArgs a = {};
-  a.interleave = RIGL_TUNE("wgrad_il", 1);
-  a.X = x; a.DY = dy; a.M = d->n * d->ho * d->wo; a.Cin = d->cin; a.Cout = d->cout; a.KH = d->kh; a.KW = d->kw;
-  a.H = d->h; a.W = d->w; a.Ho = d->ho; a.Wo = d->wo; a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_top; a.pw = d->pad_left;
+  WgradArgs a = wgrad_args(d, x, dy);
   a.tiles_ci = p.tiles_ci; a.tiles_co = p.tiles_co; a.splits = p.splits; a.slab_elems = p.slab;
-  a.x_bytes = (uint32_t)((size_t)d->n * d->h * d->w * d->cin * 2);
-  a.dy_bytes = (uint32_t)((size_t)a.M * d->cout * 2);
-  a.x_pix_stride = d->cin;
   a.fd_wo = make_fastdiv(d->wo); a.fd_ho = make_fastdiv(d->ho);
   a.OUT = p.splits > 1 ? static_cast<float*>(workspace) : dw;
   return a;

@@ -714,9 +714,10 @@ def _k2_call(name):
 
 
 # entry point -> how its (need, call) is made.  The size check of each was read in the source: conv.hip fwd_impl (tiny- / small-
-# Cin layers only: after the argument checks, before k_pad_input4 / k_im2col), rigl_masked_conv2d_wgrad (before its first
-# launch), bwd_impl (at the head of each of its six paths, before that path's launch; the paths without one of their own end
-# in rigl_masked_conv2d_wgrad), rigl_masked_conv2d_bwd_bnapply, conv_f32.hip, depthwise.hip (each right after the NULL checks).
+# Cin layers only: after the argument checks, before k_pad_input4 / k_im2col), wgrad_impl (the body of rigl_masked_conv2d_wgrad:
+# before its first launch), bwd_impl (at the head of each path that launches itself -- bwd1x1, bwdslice and the two shared
+# launches --, before that path's launch; the row-streaming and c3x3 paths and the two-launch tail go through wgrad_impl),
+# rigl_masked_conv2d_bwd_bnapply, conv_f32.hip, depthwise.hip (each right after the NULL checks).
 REFUSALS = [
     ('rigl_masked_conv2d_fwd', lambda n: _conv_call(n, SMALL_CIN, 0)),
     ('rigl_masked_conv2d_fwd_stats', lambda n: _conv_call(n, TINY_CIN, 0)),
