@@ -300,6 +300,103 @@ int rigl_masked_adam(int64_t n, float* w, float* m, float* v,
 int rigl_adam_advance(float* beta_powers /* device [2] */, float beta1,
                       float beta2, rigl_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Device-resident learning rate.
+ * Replaces: the learning-rate subgraph TF evaluates inside every training
+ *   step -- lr_schedule(current_epoch) with its tf.where chain
+ *   (rigl/imagenet_resnet/imagenet_train_eval.py:317-330, 352-354),
+ *   tf.train.piecewise_constant (rigl/cifar_resnet/resnet_train_eval.py:
+ *   189-200, rigl/mnist/mnist_train_eval.py:249-256) and
+ *   tf.train.cosine_decay_restarts (--use_sgdr, :321-323).
+ * A captured HIP graph freezes kernel arguments, so a rate passed by value
+ * (rigl_masked_sgd_momentum's / rigl_masked_adam's `lr`) is the rate of the
+ * capture for every replay.  Here the step counter and the rate live in
+ * device memory: rigl_lr_schedule_step evaluates the schedule at *step, writes
+ * *lr_out and advances *step inside the graph, and the _dlr update entry
+ * points read the rate from that buffer -- as rigl_masked_adam reads
+ * beta_powers and rigl_dropout_fwd reads its step.
+ *
+ * The schedule is a table of at most RIGL_LR_MAX_SEGMENTS segments in
+ * ascending (non-decreasing) `start` order, passed by value to the kernel.
+ *   domain RIGL_LR_DOMAIN_STEP : x = *step (int32), compared as an integer
+ *                                with start_step; f32(*step) in arithmetic.
+ *   domain RIGL_LR_DOMAIN_EPOCH: x = f32(*step) / steps_per_epoch, ONE fp32
+ *                                division (:352-353), compared with start.
+ * The active segment is the LAST one with !(x < start); below every start the
+ * first segment is active.  For ascending starts that is the value the
+ * reference's chain `rate = tf.where(x < start, rate, const)` ends with.  A
+ * tf.train.piecewise_constant boundary b (x <= b keeps the old value) is the
+ * integer start b + 1.  Only the active segment is evaluated: an inactive
+ * one whose value would be inf or NaN (the ResNet chain's warm-up divides by
+ * its start epoch 0) never reaches the output.
+ * Every product, quotient, sum and difference below is rounded to fp32
+ * separately (no FMA contraction), in this order:
+ *   RIGL_LR_CONST : lr = c
+ *   RIGL_LR_WARMUP: lr = (c * x) / d            (:325-326; c = f32(scaled_lr *
+ *                   mult0), d = f32(start_epoch0); d == 0 is legal)
+ *   RIGL_LR_COSINE: one cycle of TF 1.15's cosine_decay_restarts, alpha = 0:
+ *                   frac = ((x / d) - sum_r) / len
+ *                   t    = pi32 * frac                     (pi32 = f32(pi))
+ *                   lr   = c * ((0.5 * m_fac) * (1 + f32(cos(double(t)))))
+ *                   c = the initial rate, d = first_decay_steps, and sum_r /
+ *                   len / m_fac the cycle's (1 - t_mul^i) / (1 - t_mul),
+ *                   t_mul^i and m_mul^i, written by the host in TF's fp32
+ *                   order: the device evaluates no log, pow or floor, and the
+ *                   cycle is the segment the comparison selects.  The cosine
+ *                   is taken in double and rounded once.
+ * rigl_lr_schedule_step: *lr_out = f(*step); *step += 1 (int32 wrap-around,
+ * as rigl_dropout_advance).  One single-lane launch.  `sched` is a HOST
+ * pointer, consumed before the call returns.  RIGL_EINVAL with nothing
+ * launched: a NULL or not 4-byte aligned pointer, n_seg outside
+ * 1..RIGL_LR_MAX_SEGMENTS, an unknown domain or kind, starts of the domain
+ * that do not ascend (a NaN start included), steps_per_epoch not finite or
+ * not > 0 in the epoch domain, a COSINE segment whose len is not > 0.
+ * ---------------------------------------------------------------------- */
+#define RIGL_LR_MAX_SEGMENTS 32
+#define RIGL_LR_DOMAIN_STEP 0
+#define RIGL_LR_DOMAIN_EPOCH 1
+#define RIGL_LR_CONST 0
+#define RIGL_LR_WARMUP 1
+#define RIGL_LR_COSINE 2
+typedef struct RiglLrSegment {
+  int32_t kind;       /* RIGL_LR_CONST / _WARMUP / _COSINE */
+  int32_t start_step; /* the start in the step domain */
+  float start;        /* the start in the epoch domain */
+  float c, d;         /* see the kinds above */
+  float sum_r, len, m_fac; /* COSINE only */
+} RiglLrSegment;
+typedef struct RiglLrSchedule {
+  int32_t n_seg;
+  int32_t domain;
+  float steps_per_epoch; /* epoch domain only */
+  int32_t reserved;
+  RiglLrSegment seg[RIGL_LR_MAX_SEGMENTS];
+} RiglLrSchedule;
+int rigl_lr_schedule_step(const RiglLrSchedule* sched /* host */,
+                          int32_t* step /* device */,
+                          float* lr_out /* device */, rigl_stream_t stream);
+
+/* rigl_masked_sgd_momentum / rigl_masked_adam with `float lr` replaced by a
+ * DEVICE pointer to one fp32, read once per lane as a uniform load (the way
+ * beta_powers is read).  The same kernel bodies: for the same fp32 value in
+ * memory they leave the same bits as the by-value entry points.  Alignment
+ * and NULL rules are theirs; in addition lr must be non-NULL and 4-byte
+ * aligned (RIGL_EINVAL otherwise).                                          */
+int rigl_masked_sgd_momentum_dlr(int64_t n, float* w, float* momentum,
+                                 const float* dense_grad,
+                                 const uint32_t* mask_bits,
+                                 const float* lr /* device */, float mu,
+                                 float weight_decay, float grad_scale,
+                                 int32_t nesterov, rigl_bf16* w_shadow,
+                                 rigl_stream_t stream);
+int rigl_masked_adam_dlr(int64_t n, float* w, float* m, float* v,
+                         const float* dense_grad, const uint32_t* mask_bits,
+                         const float* beta_powers /* device [2] */,
+                         const float* lr /* device */, float beta1,
+                         float beta2, float epsilon, float weight_decay,
+                         float grad_scale, rigl_bf16* w_shadow,
+                         rigl_stream_t stream);
+
 /* bf16 shadows of mask*W for the conv kernels:  hwio[i] = bf16(mask_i?w_i:0)
  * in flat HWIO order (dgrad operand) and ohwi = the [cout][kh*kw*cin]
  * transpose (fwd operand).  Either output may be NULL.  k = kh*kw*cin.      */

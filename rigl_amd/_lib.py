@@ -87,6 +87,23 @@ class BnInferItem(C.Structure):
               ('scale_shift', C.c_void_p), ('c', C.c_int32), ('eps', C.c_float)]
 
 
+LR_MAX_SEGMENTS = 32
+LR_DOMAIN_STEP, LR_DOMAIN_EPOCH = 0, 1
+LR_CONST, LR_WARMUP, LR_COSINE = 0, 1, 2
+
+
+class LrSegment(C.Structure):
+  """RiglLrSegment: one segment of a learning-rate schedule."""
+  _fields_ = [('kind', C.c_int32), ('start_step', C.c_int32), ('start', C.c_float), ('c', C.c_float), ('d', C.c_float),
+              ('sum_r', C.c_float), ('len', C.c_float), ('m_fac', C.c_float)]
+
+
+class LrSchedule(C.Structure):
+  """RiglLrSchedule: the segment table rigl_lr_schedule_step evaluates on the device."""
+  _fields_ = [('n_seg', C.c_int32), ('domain', C.c_int32), ('steps_per_epoch', C.c_float), ('reserved', C.c_int32),
+              ('seg', LrSegment * LR_MAX_SEGMENTS)]
+
+
 class ProfLaunch(C.Structure):
   """RiglProfLaunch: one timed K1 / K2 / K3 dispatch."""
   _fields_ = [('kind', C.c_int32), ('tag', C.c_int32 * 6), ('ms', C.c_float)]
@@ -118,6 +135,9 @@ SIGNATURES = {
                                            _I32, _P, _P]),
     'rigl_masked_adam': (C.c_int, [_I64, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P, _P]),
     'rigl_adam_advance': (C.c_int, [_P, _F, _F, _P]),
+    'rigl_lr_schedule_step': (C.c_int, [C.POINTER(LrSchedule), _P, _P, _P]),
+    'rigl_masked_sgd_momentum_dlr': (C.c_int, [_I64, _P, _P, _P, _P, _P, _F, _F, _F, _I32, _P, _P]),
+    'rigl_masked_adam_dlr': (C.c_int, [_I64, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P, _P]),
     'rigl_pack_weights': (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
     'rigl_pack_weights_batched': (C.c_int, [C.POINTER(PackLayer), _I32, _P]),
     'rigl_conv2d_workspace_bytes': (_SZ, [C.POINTER(ConvDesc), _I32]),

@@ -52,6 +52,7 @@ struct SgdArgs {
   float lr, mu, wd, gscale;
   int nesterov;
   uint16_t* shadow;
+  const float* lr_dev;  // device rate of the _dlr entry point (replaces lr inside the kernel), else unused
 };
 
 __device__ __forceinline__ void sgd_one(float& w, float& a, float g, bool on, const SgdArgs& A, bool has_mom) {
@@ -70,8 +71,11 @@ __device__ __forceinline__ void sgd_one(float& w, float& a, float g, bool on, co
   }
 }
 
-template <bool HAS_MOM, bool HAS_MASK, bool HAS_SHADOW>
+// DLR: the rate is read from device memory, once per lane (a uniform load, as k_adam reads beta_powers) -- a captured graph
+// replays the CURRENT rate, not the kernel argument of the capture.  Everything after that load is the one body.
+template <bool HAS_MOM, bool HAS_MASK, bool HAS_SHADOW, bool DLR = false>
 __global__ __launch_bounds__(BLOCK) void k_sgd(SgdArgs A) {
+  if (DLR) A.lr = *A.lr_dev;
   const int64_t nq = A.n >> 2;  // full quads
   const int64_t stride = (int64_t)gridDim.x * BLOCK;
   for (int64_t qi = (int64_t)blockIdx.x * BLOCK + threadIdx.x; qi < nq; qi += stride) {
@@ -121,6 +125,7 @@ struct AdamArgs {
   const float* beta_powers;  // device {beta1^t, beta2^t}: read here, never a kernel argument (graph replay)
   float lr, omb1, omb2, eps, wd, gscale;  // omb = (1 - beta), one fp32 subtraction each on the host
   uint16_t* shadow;
+  const float* lr_dev;  // device rate of the _dlr entry point (replaces lr inside the kernel), else unused
 };
 
 // Correctly rounded fp32 sqrt.  (HIP's __fsqrt_rn is the approximate native sqrt unless OCML_BASIC_ROUNDED_OPERATIONS is
@@ -137,8 +142,9 @@ __device__ __forceinline__ void adam_one(float& w, float& m, float& v, float g, 
   w = __fsub_rn(w, __fdiv_rn(__fmul_rn(m, alpha), __fadd_rn(sqrt_rn(v), A.eps)));
 }
 
-template <bool HAS_MASK, bool HAS_SHADOW>
+template <bool HAS_MASK, bool HAS_SHADOW, bool DLR = false>
 __global__ __launch_bounds__(BLOCK) void k_adam(AdamArgs A) {
+  if (DLR) A.lr = *A.lr_dev;                // as k_sgd
   // alpha = (lr * sqrt(1 - beta2^t)) / (1 - beta1^t), in the order of ApplyAdam's functor, once per lane (uniform loads)
   const float bp1 = A.beta_powers[0], bp2 = A.beta_powers[1];
   const float alpha = __fdiv_rn(__fmul_rn(A.lr, sqrt_rn(__fsub_rn(1.f, bp2))), __fsub_rn(1.f, bp1));
@@ -313,25 +319,29 @@ int rigl_mask_unpack(const uint32_t* bits, float* mask01, int64_t n, rigl_stream
   return RIGL_OK;
 }
 
-int rigl_masked_sgd_momentum(int64_t n, float* w, float* momentum, const float* dense_grad,
-                             const uint32_t* mask_bits, float lr, float mu, float weight_decay, float grad_scale,
-                             int32_t nesterov, rigl_bf16* w_shadow, rigl_stream_t stream) {
+}  // extern "C"
+
+// The by-value and the device-rate entry points share everything: `lr_dev` non-NULL selects the DLR instantiations.
+static int sgd_launch(const char* who, int64_t n, float* w, float* momentum, const float* dense_grad,
+                      const uint32_t* mask_bits, float lr, const float* lr_dev, float mu, float weight_decay,
+                      float grad_scale, int32_t nesterov, rigl_bf16* w_shadow, rigl_stream_t stream) {
   using namespace rigl;
-  if (n < 0 || (n > 0 && (!w || !dense_grad))) return fail(RIGL_EINVAL, "rigl_masked_sgd_momentum: bad arguments");
+  if (n < 0 || (n > 0 && (!w || !dense_grad))) return fail(RIGL_EINVAL, "%s: bad arguments", who);
   if (n == 0) return RIGL_OK;
   auto mis = [](const void* p, size_t a) { return p && (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
   if (mis(w, 16) || mis(momentum, 16) || mis(dense_grad, 16) || mis(w_shadow, 8) || mis(mask_bits, 4))
-    return fail(RIGL_EINVAL, "rigl_masked_sgd_momentum: w/momentum/grad must be 16-byte aligned, shadow 8-byte");
+    return fail(RIGL_EINVAL, "%s: w/momentum/grad must be 16-byte aligned, shadow 8-byte", who);
   k3::SgdArgs A;
   A.n = n; A.w = w; A.mom = momentum; A.g = dense_grad; A.mask = mask_bits;
   A.lr = lr; A.mu = mu; A.wd = weight_decay; A.gscale = grad_scale; A.nesterov = nesterov; A.shadow = w_shadow;
+  A.lr_dev = lr_dev;
   int64_t blocks = ceil_div64(ceil_div64(n, 4), k3::BLOCK);
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   hipStream_t s = as_stream(stream);
   ProfScope prof(PROF_SGD, s);
   dim3 g((unsigned)blocks), b(k3::BLOCK);
-  const int sel = (momentum ? 4 : 0) | (mask_bits ? 2 : 0) | (w_shadow ? 1 : 0);
+  const int sel = (lr_dev ? 8 : 0) | (momentum ? 4 : 0) | (mask_bits ? 2 : 0) | (w_shadow ? 1 : 0);
   switch (sel) {
     case 0: hipLaunchKernelGGL((k3::k_sgd<false, false, false>), g, b, 0, s, A); break;
     case 1: hipLaunchKernelGGL((k3::k_sgd<false, false, true>), g, b, 0, s, A); break;
@@ -340,42 +350,93 @@ int rigl_masked_sgd_momentum(int64_t n, float* w, float* momentum, const float* 
     case 4: hipLaunchKernelGGL((k3::k_sgd<true, false, false>), g, b, 0, s, A); break;
     case 5: hipLaunchKernelGGL((k3::k_sgd<true, false, true>), g, b, 0, s, A); break;
     case 6: hipLaunchKernelGGL((k3::k_sgd<true, true, false>), g, b, 0, s, A); break;
-    default: hipLaunchKernelGGL((k3::k_sgd<true, true, true>), g, b, 0, s, A); break;
+    case 7: hipLaunchKernelGGL((k3::k_sgd<true, true, true>), g, b, 0, s, A); break;
+    case 8: hipLaunchKernelGGL((k3::k_sgd<false, false, false, true>), g, b, 0, s, A); break;
+    case 9: hipLaunchKernelGGL((k3::k_sgd<false, false, true, true>), g, b, 0, s, A); break;
+    case 10: hipLaunchKernelGGL((k3::k_sgd<false, true, false, true>), g, b, 0, s, A); break;
+    case 11: hipLaunchKernelGGL((k3::k_sgd<false, true, true, true>), g, b, 0, s, A); break;
+    case 12: hipLaunchKernelGGL((k3::k_sgd<true, false, false, true>), g, b, 0, s, A); break;
+    case 13: hipLaunchKernelGGL((k3::k_sgd<true, false, true, true>), g, b, 0, s, A); break;
+    case 14: hipLaunchKernelGGL((k3::k_sgd<true, true, false, true>), g, b, 0, s, A); break;
+    default: hipLaunchKernelGGL((k3::k_sgd<true, true, true, true>), g, b, 0, s, A); break;
   }
-  RIGL_CHECK_LAUNCH("rigl_masked_sgd_momentum");
+  RIGL_CHECK_LAUNCH(who);
   return RIGL_OK;
 }
 
-int rigl_masked_adam(int64_t n, float* w, float* m, float* v, const float* dense_grad, const uint32_t* mask_bits,
-                     const float* beta_powers, float lr, float beta1, float beta2, float epsilon, float weight_decay,
-                     float grad_scale, rigl_bf16* w_shadow, rigl_stream_t stream) {
+static bool bad_lr_dev(const float* lr) { return !lr || (reinterpret_cast<uintptr_t>(lr) & 3u) != 0; }
+
+extern "C" {
+
+int rigl_masked_sgd_momentum(int64_t n, float* w, float* momentum, const float* dense_grad,
+                             const uint32_t* mask_bits, float lr, float mu, float weight_decay, float grad_scale,
+                             int32_t nesterov, rigl_bf16* w_shadow, rigl_stream_t stream) {
+  return sgd_launch("rigl_masked_sgd_momentum", n, w, momentum, dense_grad, mask_bits, lr, nullptr, mu, weight_decay,
+                    grad_scale, nesterov, w_shadow, stream);
+}
+
+int rigl_masked_sgd_momentum_dlr(int64_t n, float* w, float* momentum, const float* dense_grad,
+                                 const uint32_t* mask_bits, const float* lr, float mu, float weight_decay,
+                                 float grad_scale, int32_t nesterov, rigl_bf16* w_shadow, rigl_stream_t stream) {
+  if (bad_lr_dev(lr)) return rigl::fail(RIGL_EINVAL, "rigl_masked_sgd_momentum_dlr: lr must be a 4-byte aligned device pointer");
+  return sgd_launch("rigl_masked_sgd_momentum_dlr", n, w, momentum, dense_grad, mask_bits, 0.f, lr, mu, weight_decay,
+                    grad_scale, nesterov, w_shadow, stream);
+}
+
+}  // extern "C"
+
+static int adam_launch(const char* who, int64_t n, float* w, float* m, float* v, const float* dense_grad,
+                       const uint32_t* mask_bits, const float* beta_powers, float lr, const float* lr_dev, float beta1,
+                       float beta2, float epsilon, float weight_decay, float grad_scale, rigl_bf16* w_shadow,
+                       rigl_stream_t stream) {
   using namespace rigl;
   if (n < 0 || (n > 0 && (!w || !m || !v || !dense_grad || !beta_powers)))
-    return fail(RIGL_EINVAL, "rigl_masked_adam: bad arguments");
+    return fail(RIGL_EINVAL, "%s: bad arguments", who);
   if (n == 0) return RIGL_OK;
   auto mis = [](const void* p, size_t a) { return p && (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
   if (mis(w, 16) || mis(m, 16) || mis(v, 16) || mis(dense_grad, 16) || mis(w_shadow, 8) || mis(mask_bits, 4) ||
       mis(beta_powers, 4))
-    return fail(RIGL_EINVAL, "rigl_masked_adam: w/m/v/grad must be 16-byte aligned, shadow 8-byte");
+    return fail(RIGL_EINVAL, "%s: w/m/v/grad must be 16-byte aligned, shadow 8-byte", who);
   k3::AdamArgs A;
   A.n = n; A.w = w; A.m = m; A.v = v; A.g = dense_grad; A.mask = mask_bits; A.beta_powers = beta_powers;
   A.lr = lr; A.omb1 = 1.f - beta1; A.omb2 = 1.f - beta2; A.eps = epsilon; A.wd = weight_decay; A.gscale = grad_scale;
-  A.shadow = w_shadow;
+  A.shadow = w_shadow; A.lr_dev = lr_dev;
   int64_t blocks = ceil_div64(ceil_div64(n, 4), k3::BLOCK);
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   hipStream_t s = as_stream(stream);
   ProfScope prof(PROF_ADAM, s);
   dim3 g((unsigned)blocks), b(k3::BLOCK);
-  const int sel = (mask_bits ? 2 : 0) | (w_shadow ? 1 : 0);
+  const int sel = (lr_dev ? 4 : 0) | (mask_bits ? 2 : 0) | (w_shadow ? 1 : 0);
   switch (sel) {
     case 0: hipLaunchKernelGGL((k3::k_adam<false, false>), g, b, 0, s, A); break;
     case 1: hipLaunchKernelGGL((k3::k_adam<false, true>), g, b, 0, s, A); break;
     case 2: hipLaunchKernelGGL((k3::k_adam<true, false>), g, b, 0, s, A); break;
-    default: hipLaunchKernelGGL((k3::k_adam<true, true>), g, b, 0, s, A); break;
+    case 3: hipLaunchKernelGGL((k3::k_adam<true, true>), g, b, 0, s, A); break;
+    case 4: hipLaunchKernelGGL((k3::k_adam<false, false, true>), g, b, 0, s, A); break;
+    case 5: hipLaunchKernelGGL((k3::k_adam<false, true, true>), g, b, 0, s, A); break;
+    case 6: hipLaunchKernelGGL((k3::k_adam<true, false, true>), g, b, 0, s, A); break;
+    default: hipLaunchKernelGGL((k3::k_adam<true, true, true>), g, b, 0, s, A); break;
   }
-  RIGL_CHECK_LAUNCH("rigl_masked_adam");
+  RIGL_CHECK_LAUNCH(who);
   return RIGL_OK;
+}
+
+extern "C" {
+
+int rigl_masked_adam(int64_t n, float* w, float* m, float* v, const float* dense_grad, const uint32_t* mask_bits,
+                     const float* beta_powers, float lr, float beta1, float beta2, float epsilon, float weight_decay,
+                     float grad_scale, rigl_bf16* w_shadow, rigl_stream_t stream) {
+  return adam_launch("rigl_masked_adam", n, w, m, v, dense_grad, mask_bits, beta_powers, lr, nullptr, beta1, beta2, epsilon,
+                     weight_decay, grad_scale, w_shadow, stream);
+}
+
+int rigl_masked_adam_dlr(int64_t n, float* w, float* m, float* v, const float* dense_grad, const uint32_t* mask_bits,
+                         const float* beta_powers, const float* lr, float beta1, float beta2, float epsilon,
+                         float weight_decay, float grad_scale, rigl_bf16* w_shadow, rigl_stream_t stream) {
+  if (bad_lr_dev(lr)) return rigl::fail(RIGL_EINVAL, "rigl_masked_adam_dlr: lr must be a 4-byte aligned device pointer");
+  return adam_launch("rigl_masked_adam_dlr", n, w, m, v, dense_grad, mask_bits, beta_powers, 0.f, lr, beta1, beta2, epsilon,
+                     weight_decay, grad_scale, w_shadow, stream);
 }
 
 int rigl_adam_advance(float* beta_powers, float beta1, float beta2, rigl_stream_t stream) {

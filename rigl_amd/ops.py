@@ -261,9 +261,22 @@ def magnitude_prune_batched(items, threshold_decay=0.0, counts=None):
 # ----------------------------------------------------------------------------
 # K3
 # ----------------------------------------------------------------------------
-def masked_sgd_momentum(w, grad, lr, momentum=None, mask_bits=None, mu=0.0,
+def _lr_device(lr, lr_device):
+  """Exactly one of ``lr`` (a host number, a kernel argument) and ``lr_device`` (fp32 [1] on the GPU, read by the kernel)."""
+  if (lr is None) == (lr_device is None):
+    raise ValueError('pass exactly one of lr and lr_device')
+  if lr_device is not None:
+    _req(lr_device, torch.float32, 'lr_device')
+    if lr_device.numel() != 1:
+      raise ValueError('lr_device must hold 1 float')
+
+
+def masked_sgd_momentum(w, grad, lr=None, momentum=None, mask_bits=None, mu=0.0,
                         weight_decay=0.0, grad_scale=1.0, nesterov=False,
-                        w_shadow=None):
+                        w_shadow=None, lr_device=None):
+  """K3 (rigl_masked_sgd_momentum).  ``lr_device`` (exclusive with ``lr``): the rate is read from that device tensor
+  (rigl_masked_sgd_momentum_dlr), so a captured graph replays the value ``lr_schedule_step`` last wrote."""
+  _lr_device(lr, lr_device)
   _req(w, torch.float32, 'w')
   _req(grad, torch.float32, 'grad')
   _req(momentum, torch.float32, 'momentum', allow_none=True)
@@ -272,16 +285,24 @@ def masked_sgd_momentum(w, grad, lr, momentum=None, mask_bits=None, mu=0.0,
   n = w.numel()
   if grad.numel() != n or (momentum is not None and momentum.numel() != n):
     raise ValueError('size mismatch')
+  if lr_device is not None:
+    check(_lib.load().rigl_masked_sgd_momentum_dlr(
+        n, _ptr(w), _ptr(momentum), _ptr(grad), _ptr(mask_bits), _ptr(lr_device),
+        float(mu), float(weight_decay), float(grad_scale), int(bool(nesterov)),
+        _ptr(w_shadow), _stream()))
+    return
   check(_lib.load().rigl_masked_sgd_momentum(
       n, _ptr(w), _ptr(momentum), _ptr(grad), _ptr(mask_bits), float(lr),
       float(mu), float(weight_decay), float(grad_scale), int(bool(nesterov)),
       _ptr(w_shadow), _stream()))
 
 
-def masked_adam(w, grad, m, v, beta_powers, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, mask_bits=None,
-                weight_decay=0.0, grad_scale=1.0, w_shadow=None):
+def masked_adam(w, grad, m, v, beta_powers, lr=None, beta1=0.9, beta2=0.999, epsilon=1e-8, mask_bits=None,
+                weight_decay=0.0, grad_scale=1.0, w_shadow=None, lr_device=None):
   """K3-Adam (rigl_masked_adam): one TF ApplyAdam step on w / m / v in place; the bias correction is read from the
-  DEVICE tensor ``beta_powers`` (fp32 [2]), which ``adam_advance`` moves on once per step."""
+  DEVICE tensor ``beta_powers`` (fp32 [2]), which ``adam_advance`` moves on once per step.  ``lr_device`` (exclusive with
+  ``lr``): the rate is read from that device tensor as well (rigl_masked_adam_dlr)."""
+  _lr_device(lr, lr_device)
   _req(w, torch.float32, 'w')
   _req(grad, torch.float32, 'grad')
   _req(m, torch.float32, 'm')
@@ -296,6 +317,11 @@ def masked_adam(w, grad, m, v, beta_powers, lr, beta1=0.9, beta2=0.999, epsilon=
     raise ValueError('mask_bits too small')
   if w_shadow is not None and w_shadow.numel() != n:
     raise ValueError('w_shadow size mismatch')
+  if lr_device is not None:
+    check(_lib.load().rigl_masked_adam_dlr(
+        n, _ptr(w), _ptr(m), _ptr(v), _ptr(grad), _ptr(mask_bits), _ptr(beta_powers), _ptr(lr_device), float(beta1),
+        float(beta2), float(epsilon), float(weight_decay), float(grad_scale), _ptr(w_shadow), _stream()))
+    return
   check(_lib.load().rigl_masked_adam(
       n, _ptr(w), _ptr(m), _ptr(v), _ptr(grad), _ptr(mask_bits), _ptr(beta_powers), float(lr), float(beta1),
       float(beta2), float(epsilon), float(weight_decay), float(grad_scale), _ptr(w_shadow), _stream()))
@@ -307,6 +333,18 @@ def adam_advance(beta_powers, beta1=0.9, beta2=0.999):
   if beta_powers.numel() != 2:
     raise ValueError('beta_powers must hold 2 floats')
   check(_lib.load().rigl_adam_advance(_ptr(beta_powers), float(beta1), float(beta2), _stream()))
+
+
+def lr_schedule_step(sched, step, lr_out):
+  """lr_out[0] = sched(step[0]); step[0] += 1, on the device (rigl_lr_schedule_step).  ``sched``: an _lib.LrSchedule (what
+  schedules.Schedule.descriptor() returns), ``step``: int32 [1], ``lr_out``: fp32 [1]."""
+  if not isinstance(sched, _lib.LrSchedule):
+    raise TypeError('sched: expected an LrSchedule descriptor, got %s' % type(sched).__name__)
+  _req(step, torch.int32, 'step')
+  _req(lr_out, torch.float32, 'lr_out')
+  if step.numel() != 1 or lr_out.numel() != 1:
+    raise ValueError('step and lr_out must hold 1 element each')
+  check(_lib.load().rigl_lr_schedule_step(C.byref(sched), _ptr(step), _ptr(lr_out), _stream()))
 
 
 def pack_weights_batched(layers):

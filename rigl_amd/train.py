@@ -15,10 +15,16 @@ gradient arena); ``apply_gradients`` enqueues one update launch per arena
 segment:  masked kernels (bitmap, weight decay) | dense kernels | BN & biases.
 The l2 regulariser's gradient (scale * w on the raw variable) is
 applied inside the kernel rather than through the loss.
+
+``learning_rate``: a float, a callable ``lr(global_step) -> float`` evaluated on the host every step (both reach the
+kernels by value), or a ``schedules.Schedule``.  On a GPU graph a Schedule takes the DEVICE path: the step counter and
+the rate live in device memory, one ``ops.lr_schedule_step`` per apply evaluates the schedule there, and the update
+kernels read the rate through a pointer -- so ``GraphedStep`` replays one graph through the whole schedule.
 """
 import torch
 
 from rigl_amd import ops
+from rigl_amd import schedules
 from rigl_amd import variables as V
 
 
@@ -30,6 +36,11 @@ def _lr_value(lr, global_step):
   if callable(lr):
     return float(lr(int(global_step.value) if global_step is not None else 0))
   return float(lr)
+
+
+def _int32(v):
+  """v as the device's int32 counter holds it (two's-complement wrap-around)."""
+  return (int(v) + 2 ** 31) % 2 ** 32 - 2 ** 31
 
 
 class Optimizer:
@@ -69,6 +80,10 @@ class GradientDescentOptimizer(Optimizer):
     self._grad_sync = grad_sync    # rigl_amd.dist.GradSync or None
     self._backward_done_for = None
     self.dense_masked_update = False   # DNW: apply the dense gradient to masked kernels too
+    # the device path of a schedules.Schedule: int32 [1] step counter, fp32 [1] rate, and what the counter holds (host mirror)
+    self._lr_step = None
+    self._lr_dev = None
+    self._lr_mirror = 0
 
   # ---- gradients -------------------------------------------------------------
   def compute_gradients(self, loss, var_list=None, **kwargs):
@@ -92,7 +107,43 @@ class GradientDescentOptimizer(Optimizer):
 
   # ---- update ----------------------------------------------------------------
   def _ensure_slots(self):
-    pass
+    self._ensure_lr_buffers()
+
+  def lr_on_device(self):
+    """True when the learning rate is a schedules.Schedule and the graph lives on a GPU: the rate is then computed and
+    read on the device (see the module docstring).  ``Schedule.host_only()`` forces the host path."""
+    w = self.graph.W
+    return isinstance(self._lr, schedules.Schedule) and w is not None and w.is_cuda
+
+  def _ensure_lr_buffers(self):
+    """The persistent step / rate buffers of the device path.  First reached in an eager step (GraphedStep runs eager steps
+    before it captures), so they never belong to a graph-private pool."""
+    if self._lr_step is None and self.lr_on_device():
+      dev = self.graph.W.device
+      self._lr_step = torch.zeros(1, dtype=torch.int32, device=dev)
+      self._lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+      self._lr_mirror = 0
+
+  def _advance_lr_mirror(self, k):
+    """The device counter moved by ``k`` without this optimizer's doing (a graph replay: +1; undoing a capture's host side
+    effect: -1)."""
+    self._lr_mirror = _int32(self._lr_mirror + k)
+
+  def _device_lr_step(self, global_step):
+    """Enqueues this step's rate: *lr = schedule(*step); *step += 1.  Invariant: before it, the device counter equals
+    global_step.value (with global_step None it free-runs from 0).  Where the host mirror of the counter says otherwise --
+    after global_step.assign, a checkpoint restore, a wrapper that stepped it some other way -- the counter is uploaded
+    first; never during stream capture, where the upload would be replayed with its frozen value."""
+    if global_step is not None:
+      want = _int32(global_step.value)
+      if want != self._lr_mirror:
+        if torch.cuda.is_current_stream_capturing():
+          raise RuntimeError('the device step counter (%d) differs from global_step (%d) during graph capture: run one eager '
+                             'step after changing global_step' % (self._lr_mirror, want))
+        self._lr_step.fill_(want)
+        self._lr_mirror = want
+    ops.lr_schedule_step(self._lr.descriptor(), self._lr_step, self._lr_dev)
+    self._advance_lr_mirror(1)
 
   def apply_gradients(self, grads_and_vars, global_step=None, name=None):
     del name
@@ -118,7 +169,11 @@ class GradientDescentOptimizer(Optimizer):
         raise NotImplementedError('apply_gradients: the fused update covers every trainable variable; missing %s%s'
                                   % (missing[:3], ' ...' if len(missing) > 3 else ''))
     self._ensure_slots()
-    lr = _lr_value(self._lr, global_step)
+    if self.lr_on_device():
+      self._device_lr_step(global_step)
+      lr = None                      # the update launches read self._lr_dev
+    else:
+      lr = _lr_value(self._lr, global_step)
     scale = self._grad_sync.grad_scale if self._grad_sync is not None else 1.0
     mu = float(self._momentum) if self._momentum is not None else 0.0
     # one launch per segment; weight decay is uniform inside a kernel segment
@@ -159,10 +214,10 @@ class GradientDescentOptimizer(Optimizer):
                         scale)
 
   def _apply_range(self, b, e, mask_bits, lr, mu, wd, scale):
-    """One update launch over arena elements [b, e) (K3)."""
+    """One update launch over arena elements [b, e) (K3).  ``lr`` None: the rate is read from the device buffer."""
     g = self.graph
     ops.masked_sgd_momentum(
-        g.W[b:e], g.G[b:e], lr,
+        g.W[b:e], g.G[b:e], lr, lr_device=self._lr_dev if lr is None else None,
         momentum=self._slot[b:e] if self._slot is not None else None,
         mask_bits=mask_bits, mu=mu, weight_decay=wd, grad_scale=scale, nesterov=self._nesterov)
 
@@ -185,6 +240,7 @@ class MomentumOptimizer(GradientDescentOptimizer):
 
   def _ensure_slots(self):
     g = self.graph
+    self._ensure_lr_buffers()
     if self._slot is None or self._slot.numel() != g.W.numel():
       old = self._slot
       self._slot = torch.zeros_like(g.W)
@@ -225,6 +281,7 @@ class AdamOptimizer(GradientDescentOptimizer):
 
   def _ensure_slots(self):
     g = self.graph
+    self._ensure_lr_buffers()
     if self._slot is None or self._slot.numel() != g.W.numel():
       if self._slot is not None:
         raise RuntimeError('variables were added after the Adam slots were created')
@@ -251,8 +308,8 @@ class AdamOptimizer(GradientDescentOptimizer):
     del mu
     g = self.graph
     ops.masked_adam(g.W[b:e], g.G[b:e], self._slot[b:e], self._slot_v[b:e], self._beta_powers, lr,
-                    beta1=self._beta1, beta2=self._beta2, epsilon=self._epsilon, mask_bits=mask_bits,
-                    weight_decay=wd, grad_scale=scale)
+                    lr_device=self._lr_dev if lr is None else None, beta1=self._beta1, beta2=self._beta2,
+                    epsilon=self._epsilon, mask_bits=mask_bits, weight_decay=wd, grad_scale=scale)
 
   def _finish(self):
     ops.adam_advance(self._beta_powers, self._beta1, self._beta2)
@@ -268,9 +325,16 @@ class GraphedStep:
   Only ORDINARY iterations are replayed: the schedule (``is_mask_update_iter``) is host arithmetic on the
   global step, so it is evaluated before every call and mask-update iterations (one in ``frequency``) run
   eagerly -- they change the masks the captured kernels read through the same buffers, which is fine: the
-  graph holds pointers, not values.  Scalars that are kernel ARGUMENTS are frozen at capture: the learning
-  rate (a new graph is captured whenever ``lr(global_step)`` changes: piecewise-constant schedules recapture
-  a handful of times) and the gradient scale.  The loss tensor returned is the captured step's output buffer.
+  graph holds pointers, not values.  Scalars that are kernel ARGUMENTS are frozen at capture: the gradient
+  scale, and a learning rate given as a float or a plain callable (a new graph is captured whenever
+  ``lr(global_step)`` changes: piecewise-constant schedules recapture a handful of times; while the value
+  changes every step -- a warm-up, a cosine -- nothing is captured and the steps run eagerly).  A learning rate
+  given as a ``schedules.Schedule`` is NOT frozen: the optimizer keeps the step counter and the rate in device
+  memory and the captured step itself evaluates the schedule and advances the counter (ops.lr_schedule_step), so
+  ONE graph, keyed on the schedule object, is replayed through warm-up, drops and restarts alike.  A replay
+  moves the optimizer's host mirror of that counter together with the global step; when the two disagree
+  (``global_step.assign``, a checkpoint restore) the call runs eagerly, which uploads the counter -- a graph is
+  never replayed against a stale counter.  The loss tensor returned is the captured step's output buffer.
 
   ``loss_fn`` must read its inputs from fixed device buffers (copy each new batch into them).  Data-parallel
   steps (a GradSync with world > 1) are not captured -- the collectives stay eager -- and run as usual.
@@ -281,7 +345,7 @@ class GraphedStep:
     self._opt = optimizer
     self._gs = global_step
     self._warmup = warmup
-    self._graphs = {}          # lr value -> (CUDAGraph, loss tensor)
+    self._graphs = {}          # lr value (or the Schedule object on the device path) -> (CUDAGraph, loss tensor)
     inner = getattr(optimizer, '_optimizer', optimizer)
     self._inner = inner
     sync = getattr(inner, '_grad_sync', None)
@@ -308,7 +372,14 @@ class GraphedStep:
   def __call__(self):
     if self._eager_only or self._is_update():
       return self._eager()
-    key = _lr_value(self._inner._lr, self._gs)                   # pylint: disable=protected-access
+    inner = self._inner
+    dev_lr = inner.lr_on_device() if hasattr(inner, 'lr_on_device') else False
+    if dev_lr:
+      if inner._lr_step is None or _int32(self._gs.value) != inner._lr_mirror:   # pylint: disable=protected-access
+        return self._eager()                                       # allocates / uploads the device counter (never in a graph)
+      key = inner._lr                                              # pylint: disable=protected-access
+    else:
+      key = _lr_value(inner._lr, self._gs)                         # pylint: disable=protected-access
     if self._ws_gen != ops.WORKSPACE_GENERATION:
       # a scratch buffer was (re)allocated since the graphs were captured (an eager mask update outgrew one, typically):
       # EVERY cached graph may point at the old buffer -- drop them all and capture again.  Checked before every replay,
@@ -320,13 +391,14 @@ class GraphedStep:
       #  a learning rate that changes every step (linear warm-up, cosine) never reuses a graph keyed on its
       # value: while the key keeps changing, run plain eager steps and do not capture; once it has been stable for
       # `_stable_needed` consecutive steps (the constant plateaus of a piecewise schedule), capture again.
-      if key == self._last_key:
-        self._stable += 1
-      else:
-        self._stable = 0
-        self._last_key = key
-      if self._stable < self._stable_needed:
-        return self._eager()
+      if not dev_lr:                                               # (the device path has one key for the whole schedule)
+        if key == self._last_key:
+          self._stable += 1
+        else:
+          self._stable = 0
+          self._last_key = key
+        if self._stable < self._stable_needed:
+          return self._eager()
       if self._warmup > 0:                                         # allocator / workspace caches / descriptors settle first
         self._warmup -= 1
         return self._eager()
@@ -336,7 +408,7 @@ class GraphedStep:
         out = self._eager()                                        # THIS call's step, on a side stream as torch's capture recipe asks
       torch.cuda.current_stream().wait_stream(side)
       torch.cuda.synchronize()
-      if self._is_update() or _lr_value(self._inner._lr, self._gs) != key:   # pylint: disable=protected-access
+      if self._is_update() or (not dev_lr and _lr_value(inner._lr, self._gs) != key):   # pylint: disable=protected-access
         return out                                                 # the next iteration is not an ordinary one at this lr: capture later
       gen0 = ops.WORKSPACE_GENERATION
       step1 = self._gs.value
@@ -345,6 +417,8 @@ class GraphedStep:
         loss = self._loss_fn()
         self._opt.minimize(loss, self._gs)                         # capture enqueues nothing; undo its host side effect:
       self._gs.value = step1
+      if dev_lr:
+        inner._advance_lr_mirror(-1)                               # pylint: disable=protected-access
       if gen0 != ops.WORKSPACE_GENERATION or gen0 != self._ws_gen:
         # a buffer grew during the pre-capture step or the capture itself: graphs cached under other learning rates are
         # stale, and this one may hold both addresses -- keep none, the next call captures on settled buffers
@@ -356,9 +430,12 @@ class GraphedStep:
       self._graphs[key] = (graph, loss)
       return out
     graph, loss = ent
-    self._last_key, self._stable = key, self._stable_needed
+    if not dev_lr:
+      self._last_key, self._stable = key, self._stable_needed
     graph.replay()
     self._gs.value += 1
+    if dev_lr:
+      inner._advance_lr_mirror(1)                                  # pylint: disable=protected-access
     self._inner.graph.shadows_dirty = True                         # the replayed update rewrote the weights
     self.replays += 1
     return loss

@@ -1,0 +1,178 @@
+"""train.GraphedStep with a device-resident learning-rate schedule: ONE captured graph is replayed through a warm-up and a
+drop and leaves the bits of eager execution on the host path -- weights, slots, masks, losses, global step.  The set-up is
+that of test_graphed_step_gpu.py: WRN depth 10, width 1, batch 32, RigL with period 5.
+
+Calls 0, 6, 12, 18 and 24 are RigL mask updates, which neither apply nor advance the global step, so call k (between
+updates) applies step k - 1 - k // 6.  The schedules:
+  'imagenet'  imagenet_lr_schedule(mobilenet_v1) with 1.25 steps per epoch: the warm-up (8 epochs) covers steps 0..9, which
+              are calls 0..11.  The reference's table fixes the first drop at five times the warm-up's length (epoch 40 =
+              step 50), so no drop falls inside 25 calls; the assign test below crosses it.
+  'drop'      the same chain with the tenfold drop moved to epoch 12 = step 15, the step call 18's update precedes (applied
+              by call 19): warm-up, plateau and drop inside 25 calls.
+"""
+import numpy as np
+import pytest
+
+torch = pytest.importorskip('torch')
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+BATCH = 32
+
+
+def _schedule(name):
+  from rigl_amd import schedules as S
+  if name == 'imagenet':
+    return S.imagenet_lr_schedule(0.4, BATCH, num_train_images=40, model_architecture='mobilenet_v1')
+  ref = _schedule('imagenet')
+  segs = [dict(ref.segments[0]), dict(ref.segments[1])]
+  segs.append(dict(ref.segments[2], start=12.0))
+  return S.Schedule(S.EPOCH, segs, steps_per_epoch=float(ref.steps_per_epoch), name='drop')
+
+
+def _run(mode, sched, calls, optimizer='momentum', method='rigl', assign=None, warmup=2):
+  """mode: 'host' (eager, sched.host_only()), 'device' (eager, device path), 'graph' (GraphedStep, device path), or
+  'float' / 'float_graph' (a constant 0.05).  assign = (call, value): global_step.assign(value) before that call."""
+  from rigl_amd import sparse_optimizers as SO, sparse_utils, train, variables as V
+  from rigl_amd.workloads import wide_resnet
+  g = V.reset_default_graph(DEV)
+  model = wide_resnet.WideResNet(g, depth=10, width=1)
+  np.random.seed(0)
+  sparse_utils.get_mask_init_fn(g.get_masks(), 'erdos_renyi_kernel', 0.8, {})()
+  lr = 0.05 if mode.startswith('float') else (sched.host_only() if mode == 'host' else sched)
+  if optimizer == 'adam':
+    inner = train.AdamOptimizer(lr, graph=g)
+  else:
+    inner = train.MomentumOptimizer(lr, 0.9, use_nesterov=True, graph=g)
+  if method == 'rigl':
+    opt = SO.SparseRigLOptimizer(inner, 0, 1000, 5, drop_fraction=0.3, drop_fraction_anneal='cosine', noise_std=0.)
+  else:
+    # SET applies on every call and updates after the apply; GraphedStep decides from the step BEFORE the call, so this test
+    # keeps both updates (after steps 0 and 5) on eager calls: end_step 6, and warmup=4 puts the capture behind the second
+    opt = SO.SparseSETOptimizer(inner, 0, 6, 5, drop_fraction=0.3, noise_std=0.)
+  gs = g.get_or_create_global_step()
+  x, y = wide_resnet.synthetic_batch(BATCH, DEV)
+  loss_fn = lambda: model.loss(x, y)
+  st = train.GraphedStep(loss_fn, opt, gs, warmup=warmup) if mode in ('graph', 'float_graph') else None
+
+  def eager():
+    loss = loss_fn()
+    opt.minimize(loss, gs)
+    return loss
+  run = st if st is not None else eager
+  losses, rates, replay_steps = [], [], []
+  for k in range(calls):
+    if assign is not None and k == assign[0]:
+      gs.assign(assign[1])
+    r0, s0 = (st.replays if st is not None else 0), int(gs.value)
+    losses.append(float(run().detach().float()))
+    if st is not None and st.replays > r0:
+      replay_steps.append(s0)
+    if inner._lr_dev is not None:
+      rates.append((s0, int(gs.value), float(inner._lr_dev.cpu()[0])))
+  torch.cuda.synchronize()
+  out = dict(W=g.W.cpu().numpy().copy(), A=inner._slot.cpu().numpy().copy(), B=g.BITS.cpu().numpy().copy(),
+             gs=int(gs.value), losses=losses, rates=rates, replay_steps=replay_steps)
+  if optimizer == 'adam':
+    out['V'] = inner._slot_v.cpu().numpy().copy()
+  if inner._lr_step is not None:
+    out['counter'] = int(inner._lr_step.cpu()[0])
+    out['mirror'] = inner._lr_mirror
+  if st is not None:
+    out.update(replays=st.replays, eager=st.eager_steps, n_graphs=len(st._graphs), keys=list(st._graphs))
+  return out
+
+
+def _same(a, b):
+  np.testing.assert_array_equal(a['B'], b['B'])
+  for k in ('W', 'A') + (('V',) if 'V' in a else ()):
+    np.testing.assert_array_equal(a[k].view(np.uint32), b[k].view(np.uint32))
+  assert a['losses'] == b['losses']
+  assert a['gs'] == b['gs']
+
+
+def _rates_follow(out, sched):
+  """After every call that applied, the device rate is the schedule at the step it applied."""
+  n = 0
+  for s0, s1, rate in out['rates']:
+    if s1 == s0 + 1:
+      assert rate == sched(s0), (s0, rate, sched(s0))
+      n += 1
+  return n
+
+
+@pytest.mark.parametrize('name', ['imagenet', 'drop'])
+def test_one_graph_through_warmup_and_drop_is_bit_identical_to_eager(name):
+  from rigl_amd import schedules as S
+  sched = _schedule(name)
+  calls = 25
+  assert [sched.active_segment(s)[0] for s in (0, 9, 10)] == [0, 0, 1]          # the warm-up: steps 0..9
+  assert sched(9) < sched(10) and sched(1) > sched(0) == 0.0
+  if name == 'drop':
+    assert sched.active_segment(14)[0] == 1 and sched.active_segment(15)[0] == 2
+    assert abs(sched(15) / sched(14) - 0.1) < 1e-6
+  a = _run('host', sched, calls)
+  b = _run('device', sched, calls)
+  c = _run('graph', sched, calls)
+  assert a['gs'] == calls - 5
+  _same(a, b)
+  _same(a, c)
+  assert c['replays'] >= 8, c['replays']
+  in_warmup = [s for s in c['replay_steps'] if sched.segments[sched.active_segment(s)[0]]['kind'] == S.WARMUP]
+  assert len(in_warmup) >= 4, c['replay_steps']
+  assert c['n_graphs'] == 1 and c['keys'] == [sched]
+  assert c['counter'] == c['gs'] == c['mirror'] and b['counter'] == b['gs']
+  assert _rates_follow(b, sched) == calls - 5 and _rates_follow(c, sched) == calls - 5
+  if name == 'drop':
+    assert any(s >= 15 for s in c['replay_steps'])                                 # replays on both sides of the drop
+    assert any(10 <= s < 15 for s in c['replay_steps'])
+
+
+def test_adam_on_the_device_path():
+  sched = _schedule('imagenet')
+  a = _run('host', sched, 12, optimizer='adam')
+  b = _run('device', sched, 12, optimizer='adam')
+  c = _run('graph', sched, 12, optimizer='adam')
+  _same(a, b)
+  _same(a, c)
+  assert c['replays'] >= 4 and c['n_graphs'] == 1 and c['counter'] == c['gs'] == 10
+  assert _rates_follow(c, sched) == 10
+
+
+def test_set_applies_on_every_call_and_the_counter_moves_with_it():
+  sched = _schedule('drop')
+  a = _run('host', sched, 20, method='set', warmup=4)
+  b = _run('device', sched, 20, method='set', warmup=4)
+  c = _run('graph', sched, 20, method='set', warmup=4)
+  assert a['gs'] == 20
+  _same(a, b)
+  _same(a, c)
+  assert c['replays'] >= 8 and c['n_graphs'] == 1 and c['counter'] == c['gs'] == 20
+  assert _rates_follow(c, sched) == 20
+
+
+def test_assigning_the_global_step_reuploads_the_counter():
+  """gs.assign(40) between two calls: the next step trains at sched(40), no graph is replayed against the old counter (that call
+  runs eagerly and uploads), and the run goes on bit-identical to an eager twin given the same assign -- across the imagenet
+  table's own tenfold drop at step 50."""
+  sched = _schedule('imagenet')
+  assert abs(sched(50) / sched(49) - 0.1) < 1e-6
+  calls, at = 28, 10
+  a = _run('host', sched, calls, assign=(at, 40))
+  c = _run('graph', sched, calls, assign=(at, 40))
+  _same(a, c)
+  assert c['gs'] > 50 and c['counter'] == c['gs'] == c['mirror']
+  assert all(s != 40 for s in c['replay_steps'])                                   # the call that applied step 40 ran eagerly
+  applied_40 = [rate for s0, s1, rate in c['rates'] if (s0, s1) == (40, 41)]
+  assert applied_40 == [sched(40)]
+  assert any(s < 40 for s in c['replay_steps']) and any(s > 50 for s in c['replay_steps'])   # the SAME graph, before and after
+  assert c['n_graphs'] == 1
+  assert _rates_follow(c, sched) >= 20
+
+
+def test_a_float_learning_rate_behaves_as_before():
+  a = _run('float', None, 13)
+  c = _run('float_graph', None, 13)
+  _same(a, c)
+  assert c['keys'] == [0.05] and c['replays'] >= 4
+  assert 'counter' not in c and c['rates'] == []                                  # no device buffers on this path
