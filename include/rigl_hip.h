@@ -851,6 +851,78 @@ int rigl_dropout_bwd(const void* dy, const uint8_t* keep_bits, void* dx,
 int rigl_dropout_advance(int32_t* step /* device */, rigl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The CIFAR input pipeline on the device (rigl/cifar_resnet/data_helper.py:
+ * per_image_standardization, 4-pixel mirror pad, random 32x32 crop, random
+ * left-right flip, a reshuffle each pass).  32x32x3 images only.  One launch
+ * writes batch `*step` into `out` / `out_labels` / `out_index`; everything that
+ * depends on the step is derived on the device from the counter, so a captured
+ * graph that holds this launch and rigl_cifar_advance replays fresh,
+ * augmented, reshuffled batches across epoch boundaries with no host work.
+ * tests/input_ref.py restates all of the following in NumPy, bit for bit.
+ *
+ * Standardization, over the ORIGINAL image (n = 3072 bytes x), before pad and
+ * crop, on exact integer sums:
+ *   S1 = sum x, S2 = sum x^2 (int);  D = n*S2 - S1*S1 (int64, >= 0)
+ *   den = max(sqrtf((float)D), sqrtf(3072.f));  inv = 1.0f / den
+ *   y32 = (float)(n*x - S1) * inv          ((float) conversions and sqrtf, /,
+ *                                            * correctly rounded, RNE)
+ *   out = y32 (dtype 1, fp32) or y32 rounded to nearest even (dtype 0, bf16)
+ * This is tf.image.per_image_standardization, (x - mean) / max(stddev,
+ * 1/sqrt(n)), with numerator and denominator scaled by n: n*x - S1 is an exact
+ * integer below 2^24, so a low-variance image loses nothing to cancellation;
+ * a constant image gives +0 everywhere.
+ *
+ * Augmentation (mode 0, train), on the standardized image.  The padded image
+ * has coordinates 0..39 in both directions and mirrors WITH the edge pixel
+ * (NumPy 'symmetric': rows 3,2,1,0 in front, 31,30,29,28 behind):
+ *   src(p) = 3 - p (p < 4),  p - 4 (4 <= p < 36),  67 - p (p >= 36)
+ *   out[i][r][c] = y[src(r + oy)][src(c' + ox)],  c' = flip ? 31 - c : c
+ * (the crop first, then the flip of the cropped image).  Image i of the batch
+ * at step s draws from Philox block i -- words w0..w3 = elements 4i..4i+3 -- of
+ * tf.random.stateless_uniform's uint32 stream under the seed pair
+ * [seed0, s] (the GenerateKey scramble of rigl_stateless_random):
+ *   oy = w0 % 9,  ox = w1 % 9,  flip = Uint32ToFloat(w2) < 0.5f;  w3 unused.
+ *
+ * Sample order (train).  s is *step read as uint32 (a negative step counts as
+ * its bit pattern; in the seed pair above it is the int32 itself).
+ *   spe = n_images / (batch * n_shards)      steps per epoch; the last
+ *         n_images % (batch * n_shards) positions of an epoch's order are skipped
+ *   e = s / spe;   p = (s % spe) * batch * n_shards + shard * batch + i
+ *   dataset index = pi_e(p), a keyed bijection of [0, n_images):
+ *   a balanced Feistel network over 2h bits, h = max(1, ceil(bit_length(
+ *   n_images - 1) / 2)), 6 rounds, round keys k0..k5 = the first six uint32 of
+ *   the stateless stream under the seed pair [seed0 ^ 0x5eed, int32(e)]:
+ *     v = (L << h) | R;  per round r: (L, R) <- (R, L ^ (((R ^ k_r) *
+ *     0x9E3779B1u mod 2^32) >> (32 - h)));  result (L << h) | R
+ *   re-applied while the result is >= n_images (cycle walking).
+ * No permutation is stored anywhere.
+ *
+ * Eval (mode 1): no crop, flip or shuffle; *step (as uint32) is the batch
+ * index b and image i is dataset index (b * n_shards + shard) * batch + i.
+ * Images whose index is >= n_images are NOT written: a final partial batch
+ * leaves the tail of out / out_labels / out_index untouched.
+ *
+ * images: uint8 [n_images, 32, 32, 3] (HWC), labels: int32 [n_images]; both
+ * are only read.  out: [batch, 32, 32, 3] of dtype; out_labels, out_index:
+ * int32 [batch], out_index (the dataset index of each image) may be NULL.
+ * Nothing past element `batch` of the three outputs is touched.  images and
+ * out must be 16-byte aligned, the int32 arrays 4-byte.  RIGL_EINVAL, with a
+ * message and before any launch, for: batch <= 0; a NULL images / labels /
+ * step / out / out_labels; n_images <= 0 or > 2^30; mode not 0 / 1; dtype not
+ * 0 / 1; shard outside [0, n_shards); train mode with n_images < batch *
+ * n_shards; a misaligned pointer.
+ * rigl_cifar_advance: *step += 1 with int32 wrap-around, one single-lane
+ * launch, as rigl_dropout_advance.
+ * ---------------------------------------------------------------------- */
+int rigl_cifar_batch(const uint8_t* images, const int32_t* labels,
+                     int64_t n_images, int32_t batch, int32_t mode,
+                     int32_t shard, int32_t n_shards, int32_t seed0,
+                     const int32_t* step /* device */, void* out, int32_t dtype,
+                     int32_t* out_labels, int32_t* out_index /* or NULL */,
+                     rigl_stream_t stream);
+int rigl_cifar_advance(int32_t* step /* device */, rigl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Glue: max pooling, NHWC bf16 (tf.layers.max_pooling2d(3, 2, 'SAME') after the
  * stem, rigl/imagenet_resnet/resnet_model.py:637-644).  The descriptor is a
  * RiglConvDesc with cin == cout (% 8 == 0); padding explicit, windows clipped

@@ -189,6 +189,8 @@ SIGNATURES = {
     'rigl_dropout_fwd': (C.c_int, [_P, _P, _P, _I64, _I32, _F, _I32, _P, _P]),
     'rigl_dropout_bwd': (C.c_int, [_P, _P, _P, _I64, _I32, _F, _P]),
     'rigl_dropout_advance': (C.c_int, [_P, _P]),
+    'rigl_cifar_batch': (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P]),
+    'rigl_cifar_advance': (C.c_int, [_P, _P]),
     'rigl_maxpool_fwd': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P]),
     'rigl_maxpool_bwd': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P]),
     'rigl_bn_fwd_statistics': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P]),

@@ -1099,6 +1099,44 @@ def dropout_advance(step):
 
 
 # ----------------------------------------------------------------------------
+# the CIFAR input pipeline (standardize, mirror pad, crop, flip, shuffle; step counter on the device)
+# ----------------------------------------------------------------------------
+def cifar_batch(images, labels, batch, step, out, out_labels, out_index=None, train=True, seed0=0, shard=0, n_shards=1):
+  """rigl_cifar_batch: batch ``step`` of the dataset (``images`` uint8 [N, 32, 32, 3], ``labels`` int32 [N]) into ``out``
+  ([batch, 32, 32, 3], bf16 or fp32), ``out_labels`` and, when given, ``out_index`` (int32 [batch], the dataset index of each
+  image).  ``step``: DEVICE int32 [1], read by the kernel (``cifar_advance`` moves it on), so a replayed graph produces the
+  next batch.  train: standardized, mirror-padded, randomly cropped and flipped images in the epoch's keyed order; eval:
+  standardized images in dataset order, ``step`` the batch index, images past the end of the dataset left unwritten."""
+  _req(images, torch.uint8, 'images')
+  _req(labels, torch.int32, 'labels')
+  _req(step, torch.int32, 'step')
+  dt = _dropout_dtype(out, 'out')
+  _req(out_labels, torch.int32, 'out_labels')
+  _req(out_index, torch.int32, 'out_index', allow_none=True)
+  if step.numel() != 1:
+    raise ValueError('step must hold one int32')
+  if images.dim() != 4 or tuple(images.shape[1:]) != (32, 32, 3):
+    raise ValueError('images must be [N, 32, 32, 3] uint8 (HWC), got %s' % (tuple(images.shape),))
+  n = images.shape[0]
+  batch = int(batch)
+  if labels.numel() != n:
+    raise ValueError('labels must hold one int32 per image')
+  if batch > 0 and (out.numel() != batch * 3072 or out_labels.numel() != batch or
+                    (out_index is not None and out_index.numel() != batch)):
+    raise ValueError('out must be [batch, 32, 32, 3] and out_labels / out_index [batch]')
+  check(_lib.load().rigl_cifar_batch(_ptr(images), _ptr(labels), n, batch, 0 if train else 1, int(shard), int(n_shards),
+                                     _i32(seed0), _ptr(step), _ptr(out), dt, _ptr(out_labels), _ptr(out_index), _stream()))
+
+
+def cifar_advance(step):
+  """step += 1 on the device (rigl_cifar_advance), once per batch."""
+  _req(step, torch.int32, 'step')
+  if step.numel() != 1:
+    raise ValueError('step must hold one int32')
+  check(_lib.load().rigl_cifar_advance(_ptr(step), _stream()))
+
+
+# ----------------------------------------------------------------------------
 # max pooling (glue)
 # ----------------------------------------------------------------------------
 def maxpool_fwd(d, x):
