@@ -96,6 +96,9 @@ int rigl_mask_unpack(const uint32_t* bits, float* mask01, int64_t n,
  *   w[new]  = grow value;  momentum[new] = reset value;  mask = mask1 | mask2
  * drop score = |mask*w| (+ drop_noise[i], one fp32 add) unless score_drop is
  * given; grow score = |dense_grad| unless score_grow is given.
+ * Scores may be subnormal, +-inf or signed zeros (-0.0 ties with +0.0); NaN
+ * scores are out of scope: tf.nn.top_k's order on NaN is not defined.
+ * The fp32 pointers need no alignment beyond 4 bytes; bitmaps are 4-byte words.
  * ---------------------------------------------------------------------- */
 typedef struct RiglPruneRegrowLayer {
   int64_t n;               /* number of weights in this tensor (< 2^31)     */
@@ -113,7 +116,7 @@ typedef struct RiglPruneRegrowLayer {
 enum {
   RIGL_GROW_ZEROS = 0,      /* grow_init='zeros'          (:372-373)         */
   RIGL_GROW_GRAD_SCALE = 1, /* 'grad_scale_d': g / d      (:542-545)         */
-  RIGL_GROW_GRAD_SIGN = 2,  /* 'grad_sign_d': sign(g) / d (:546-549)         */
+  RIGL_GROW_GRAD_SIGN = 2,  /* 'grad_sign_d': sign(g) / d (:546-549), sign(+-0) = +0 as tf.sign */
   RIGL_GROW_EXPLICIT = 3    /* values from grow_values    (random_* / initial_dist_* drawn by the host) */
 };
 enum {
@@ -253,14 +256,26 @@ int rigl_magnitude_prune_batched(const RiglMagnitudePruneLayer* layers /* host *
  *   (rigl/imagenet_resnet/imagenet_train_eval.py:360-361,
  *    rigl/cifar_resnet/resnet_train_eval.py:202-203) together with the
  *   `mask *` of the masked-weight gradient and the l2_regularizer gradient:
- *     g  = (mask ? grad_scale*dense_grad : 0) + weight_decay * w
+ *     g  = mask * (grad_scale*dense_grad) + weight_decay * w
  *     a  = momentum*a + g
  *     w -= lr*g + lr*momentum*a   (nesterov)   |   w -= lr*a   (plain)
- *   every product / sum rounded to fp32 separately (no FMA contraction), so
- *   the result is bit-identical to the oracle.
+ *   every product / sum rounded to fp32 separately (no FMA contraction).
+ *   For finite inputs w and a are bit-identical to oracle/rigl_oracle.py's
+ *   masked_grad (on the scaled gradient) followed by momentum_apply /
+ *   sgd_apply, the signs of zeros included: the decay product is always added
+ *   (a signed zero when weight_decay == 0) and a masked-off element contributes
+ *   0 * g, a zero with the gradient's sign -- a momentum of -0.0 (RigL's reset
+ *   g * 0.0 of a negative gradient, or a pruned weight's underflowed slot)
+ *   keeps the sign the reference would give it.
+ *   The one deliberate deviation: a NON-FINITE gradient at a masked-off
+ *   position also counts as that signed zero, where the reference's 0 * inf
+ *   would write NaN into the pruned weight.  (A non-finite w is outside the
+ *   contract: 0 * w is NaN, as in the reference.)
  * mask_bits == NULL means "all ones" (dense tensors: BN, biases, dense stem).
  * momentum == NULL means plain gradient descent (w -= lr*g).
  * w_shadow (nullable) receives bf16(mask ? w_new : 0), same flat order.
+ * Alignment: w, momentum, dense_grad 16-byte, w_shadow 8-byte, mask_bits
+ * 4-byte (RIGL_EINVAL otherwise, nothing launched).
  * ---------------------------------------------------------------------- */
 int rigl_masked_sgd_momentum(int64_t n, float* w, float* momentum,
                              const float* dense_grad, const uint32_t* mask_bits,
@@ -274,12 +289,19 @@ int rigl_masked_sgd_momentum(int64_t n, float* w, float* momentum,
  *   --use_adam; mnist_train_eval.py:247-261 --optimizer=adam), together with
  *   the `mask *` of the masked-weight gradient and the l2 gradient:
  *     alpha = (lr * sqrt(1 - beta_powers[1])) / (1 - beta_powers[0])
- *     g     = (mask ? grad_scale*dense_grad : 0) + weight_decay * w
+ *     g     = mask * (grad_scale*dense_grad) + weight_decay * w
  *     m     = m + (g - m) * (1 - beta1)
  *     v     = v + (g*g - v) * (1 - beta2)
  *     w     = w - (m * alpha) / (sqrt(v) + epsilon)
  *   every product / sum rounded to fp32 separately, sqrt and division
- *   correctly rounded: bit-identical to TF's fp32 CPU kernel.
+ *   correctly rounded.  For finite inputs w, m and v are bit-identical to
+ *   tests/adam_ref.py -- the fp32 restatement of ApplyAdam's CPU functor on
+ *   oracle.masked_grad of the scaled gradient, K3's g -- which the
+ *   reference-executed trajectories of tests/golden/adam_cases.npz confirm.
+ *   (The kernel forms g by selection, which can differ from K3's g in the
+ *   sign of a zero only; no bit of m, v or w depends on that sign.)  The same
+ *   deliberate deviation: a non-finite gradient at a masked-off position
+ *   counts as zero.
  * Masked-off weights are updated too (the reference applies Adam to the raw
  * variable: a pruned weight gets g = weight_decay*w and keeps drifting on its
  * old m); w_shadow (nullable) receives bf16(mask ? w_new : 0).

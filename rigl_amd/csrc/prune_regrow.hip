@@ -741,7 +741,7 @@ __global__ __launch_bounds__(BLOCK) void k_apply2(const LayerDev* __restrict__ L
             float nw = 0.f;
             if (prm.grow_init_mode == RIGL_GROW_GRAD_SCALE) nw = __fdiv_rn(gv[v], prm.grow_init_div);
             else if (prm.grow_init_mode == RIGL_GROW_GRAD_SIGN) {
-              float sg = gv[v] > 0.f ? 1.f : (gv[v] < 0.f ? -1.f : gv[v]);  // tf.sign: sign(+-0) = +-0
+              float sg = (float)(gv[v] > 0.f) - (float)(gv[v] < 0.f);      // tf.sign (Eigen): (x > 0) - (x < 0), so sign(+-0) = +0
               nw = __fdiv_rn(sg, prm.grow_init_div);
             } else if (prm.grow_init_mode == RIGL_GROW_EXPLICIT) nw = ev[v];
             L.w[q[j].e0 + v] = nw;

@@ -4,6 +4,8 @@ product and sum is rounded to fp32 separately; sqrt and division are the
 correctly rounded fp32 operations."""
 import numpy as np
 
+from oracle import rigl_oracle as O
+
 F32 = np.float32
 
 
@@ -14,14 +16,13 @@ def alpha(lr, beta_powers):
 
 
 def masked_grad(dense, mask, w, weight_decay=0.0, grad_scale=1.0):
-  """g = (mask ? grad_scale*dense : 0) + wd*w, as rigl_masked_sgd_momentum / rigl_masked_adam form it."""
+  """g = mask * (grad_scale*dense) + wd*w: oracle.masked_grad (the reference's own form, zero signs included) on the
+  scaled gradient; mask None = all ones.  For finite inputs rigl_masked_sgd_momentum forms the same bits, and
+  rigl_masked_adam the same up to the sign of a zero, which none of its results depends on."""
   dense = np.asarray(dense, F32)
-  gm = dense if F32(grad_scale) == F32(1) else (dense * F32(grad_scale)).astype(F32)
-  if mask is not None:
-    gm = np.where(np.asarray(mask) != 0, gm, F32(0)).astype(F32)
-  if F32(weight_decay) != F32(0):
-    gm = (gm + (F32(weight_decay) * np.asarray(w, F32)).astype(F32)).astype(F32)
-  return gm
+  gs = dense if F32(grad_scale) == F32(1) else (dense * F32(grad_scale)).astype(F32)
+  m = np.ones_like(gs) if mask is None else (np.asarray(mask) != 0).astype(F32)
+  return O.masked_grad(gs, m, w, weight_decay)
 
 
 def adam_apply(w, m, v, g, lr, beta_powers, beta1=0.9, beta2=0.999, epsilon=1e-8):
