@@ -419,6 +419,67 @@ int rigl_masked_adam_dlr(int64_t n, float* w, float* m, float* v,
                          float grad_scale, rigl_bf16* w_shadow,
                          rigl_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Per-step training summaries.
+ * Replaces: the scalars every training driver of the reference hands to
+ *   tf.summary / host_call on every step -- tf.norm of the gradients and of
+ *   the variables, the fw_nz_weight / fw_nz_mask / fw_l1_weight probes and
+ *   the per-mask sparsities (rigl/imagenet_resnet/imagenet_train_eval.py:
+ *   431-473, rigl/imagenet_resnet/utils.py:59-90) -- with ONE read-only pass
+ *   over the arenas per step and a record in a device ring, so a captured
+ *   HIP graph leaves a record per replay and the host reads when it likes.
+ * One entry per trainable variable, elements [0, n) only (padding between
+ * variables is never read).  Per element, with m the mask bit (1 where
+ * mask_bits == NULL or apply_mask == 0):
+ *   gq = f32(f32(m * f32(grad_scale * g)) + f32(weight_decay * w))
+ * -- the gradient rigl_masked_sgd_momentum applies, rounding for rounding,
+ * with its documented deviation: a masked-off element contributes the signed
+ * zero of the scaled gradient, also where that gradient is not finite.
+ * Per entry (fp64 sums, integer counts):
+ *   sumsq_g = sum gq^2        sumsq_w = sum w^2 (raw weights)   l1_w = sum |w|
+ *   nz_w = #(w != 0)  (-0.0 is zero, subnormals are not)
+ *   mask_ones = popcount of bits [0, n)  (n where mask_bits == NULL)
+ *   nonfinite_g = #(gq inf or NaN)
+ * Non-finite values propagate into the sums as IEEE arithmetic gives them.
+ * DETERMINISM: every entry is cut into chunks of RIGL_SUMMARY_CHUNK elements;
+ * a chunk is reduced in a fixed order, a second launch sums an entry's chunk
+ * partials in a fixed order and the entries likewise.  No atomics; the bits of
+ * the result do not depend on max_blocks (the grid cap of the partials
+ * launches, 0 = default) or on anything but the table and the data.
+ * The finalize launch writes slot (*step mod ring_slots) of `ring`
+ * (rigl_summary_slot_bytes(n_entries) bytes per slot, 16-byte aligned):
+ *   int32 step, int32 n_entries, fp32 loss (*loss; NaN where loss == NULL),
+ *   fp32 learning rate (*lr, or lr_value where lr == NULL)       -- 16 bytes
+ *   the totals over all entries, then entry 0, 1 ...: each 3 fp64 (sumsq_g,
+ *   sumsq_w, l1_w) and 3 int64 (nz_w, mask_ones, nonfinite_g)    -- 48 bytes
+ * and then *step += 1 (int32 wrap-around, as rigl_lr_schedule_step).
+ * Capture-safe: `entries` is a HOST array, consumed before the call returns
+ * and passed to the kernels by value, 64 entries per launch; no copy is
+ * enqueued.  Launches: ceil(n_entries / 64) + 1.
+ * Refused with nothing launched: RIGL_EWORKSPACE for a workspace that is NULL
+ * or shorter than rigl_summary_workspace_bytes(entries, n_entries);
+ * RIGL_EINVAL for w / g not 16-byte aligned, mask_bits / step / loss / lr not
+ * 4-byte aligned, ring not 16-byte aligned, ring_slots < 1, n < 0, a NULL
+ * w / g with n > 0.
+ * ---------------------------------------------------------------------- */
+#define RIGL_SUMMARY_CHUNK 8192
+typedef struct RiglSummaryEntry {
+  int64_t n;
+  const float* w;            /* fp32 [n] */
+  const float* g;            /* fp32 [n]: the gradient-arena slice (dense for masked kernels) */
+  const uint32_t* mask_bits; /* ceil(n/32) words, NULL = all ones */
+  float weight_decay;
+  int32_t apply_mask;        /* 0: g is used unmasked (DNW); mask_ones still counts the bitmap */
+} RiglSummaryEntry;
+size_t rigl_summary_slot_bytes(int32_t n_entries);
+size_t rigl_summary_workspace_bytes(const RiglSummaryEntry* entries /* host */, int32_t n_entries);
+int rigl_summary_step(const RiglSummaryEntry* entries /* host */, int32_t n_entries,
+                      float grad_scale, const float* loss /* device, nullable */,
+                      const float* lr /* device, nullable */, float lr_value,
+                      int32_t* step /* device */, void* ring /* device */,
+                      int32_t ring_slots, void* workspace, size_t workspace_size /* bytes */,
+                      int32_t max_blocks, rigl_stream_t stream);
+
 /* bf16 shadows of mask*W for the conv kernels:  hwio[i] = bf16(mask_i?w_i:0)
  * in flat HWIO order (dgrad operand) and ohwi = the [cout][kh*kw*cin]
  * transpose (fwd operand).  Either output may be NULL.  k = kh*kw*cin.      */

@@ -104,6 +104,17 @@ class LrSchedule(C.Structure):
               ('seg', LrSegment * LR_MAX_SEGMENTS)]
 
 
+SUMMARY_CHUNK = 8192          # RIGL_SUMMARY_CHUNK
+SUMMARY_HEADER_BYTES = 16     # int32 step, int32 n_entries, fp32 loss, fp32 learning rate
+SUMMARY_GROUP_BYTES = 48      # 3 fp64 (sumsq_g, sumsq_w, l1_w), 3 int64 (nz_w, mask_ones, nonfinite_g): the totals, then every entry
+
+
+class SummaryEntry(C.Structure):
+  """RiglSummaryEntry: one trainable variable of rigl_summary_step."""
+  _fields_ = [('n', C.c_int64), ('w', C.c_void_p), ('g', C.c_void_p), ('mask_bits', C.c_void_p),
+              ('weight_decay', C.c_float), ('apply_mask', C.c_int32)]
+
+
 class ProfLaunch(C.Structure):
   """RiglProfLaunch: one timed K1 / K2 / K3 dispatch."""
   _fields_ = [('kind', C.c_int32), ('tag', C.c_int32 * 6), ('ms', C.c_float)]
@@ -138,6 +149,9 @@ SIGNATURES = {
     'rigl_lr_schedule_step': (C.c_int, [C.POINTER(LrSchedule), _P, _P, _P]),
     'rigl_masked_sgd_momentum_dlr': (C.c_int, [_I64, _P, _P, _P, _P, _P, _F, _F, _F, _I32, _P, _P]),
     'rigl_masked_adam_dlr': (C.c_int, [_I64, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P, _P]),
+    'rigl_summary_slot_bytes': (_SZ, [_I32]),
+    'rigl_summary_workspace_bytes': (_SZ, [C.POINTER(SummaryEntry), _I32]),
+    'rigl_summary_step': (C.c_int, [C.POINTER(SummaryEntry), _I32, _F, _P, _P, _F, _P, _P, _I32, _P, _SZ, _I32, _P]),
     'rigl_pack_weights': (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
     'rigl_pack_weights_batched': (C.c_int, [C.POINTER(PackLayer), _I32, _P]),
     'rigl_conv2d_workspace_bytes': (_SZ, [C.POINTER(ConvDesc), _I32]),

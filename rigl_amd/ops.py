@@ -347,6 +347,57 @@ def lr_schedule_step(sched, step, lr_out):
   check(_lib.load().rigl_lr_schedule_step(C.byref(sched), _ptr(step), _ptr(lr_out), _stream()))
 
 
+def summary_table(entries):
+  """The host table of rigl_summary_step: ``entries`` is a list of (w fp32 [n], g fp32 [n], mask_bits int32 | None,
+  weight_decay, apply_mask).  The table holds raw pointers: the caller keeps the tensors alive."""
+  arr = (_lib.SummaryEntry * max(len(entries), 1))()
+  for i, (w, g, bits, wd, apply_mask) in enumerate(entries):
+    _req(w, torch.float32, 'w')
+    _req(g, torch.float32, 'g')
+    _req(bits, torch.int32, 'mask_bits', allow_none=True)
+    if g.numel() != w.numel():
+      raise ValueError('summary_table: entry %d: w has %d elements, g %d' % (i, w.numel(), g.numel()))
+    if bits is not None and bits.numel() < n_mask_words(w.numel()):
+      raise ValueError('summary_table: entry %d: mask_bits too small' % i)
+    arr[i].n = w.numel()
+    arr[i].w = w.data_ptr()
+    arr[i].g = g.data_ptr()
+    arr[i].mask_bits = bits.data_ptr() if bits is not None else None
+    arr[i].weight_decay = float(wd)
+    arr[i].apply_mask = int(bool(apply_mask))
+  return arr, len(entries)
+
+
+def summary_slot_bytes(n_entries):
+  return int(_lib.load().rigl_summary_slot_bytes(int(n_entries)))
+
+
+def summary_workspace_bytes(table):
+  arr, n = table
+  return int(_lib.load().rigl_summary_workspace_bytes(arr, n))
+
+
+def summary_step(table, step, ring, ring_slots, grad_scale=1.0, loss=None, lr=None, lr_device=None, max_blocks=0):
+  """One record of the training summaries (rigl_summary_step): the sums and counts of every entry of ``table``
+  (summary_table) into slot ``step[0] % ring_slots`` of ``ring`` (uint8, ring_slots * summary_slot_bytes), then
+  ``step[0] += 1``.  ``loss``: fp32 device scalar or None; the rate is ``lr_device`` (fp32 [1] on the GPU) or the float ``lr``.
+  Enqueues kernels only (capture-safe); the scratch comes from ops.workspace."""
+  arr, n = table
+  _lr_device(lr, lr_device)
+  _req(step, torch.int32, 'step')
+  _req(ring, torch.uint8, 'ring')
+  _req(loss, torch.float32, 'loss', allow_none=True)
+  if step.numel() != 1 or (loss is not None and loss.numel() != 1):
+    raise ValueError('step and loss must hold 1 element each')
+  lib = _lib.load()
+  if ring_slots < 1 or ring.numel() < ring_slots * lib.rigl_summary_slot_bytes(n):
+    raise ValueError('ring of %d bytes is too small for %d slots of %d entries' % (ring.numel(), ring_slots, n))
+  need = lib.rigl_summary_workspace_bytes(arr, n)
+  ws = workspace(need, ring.device, 'summary')
+  check(lib.rigl_summary_step(arr, n, float(grad_scale), _ptr(loss), _ptr(lr_device), float(lr if lr is not None else 0.0),
+                              _ptr(step), _ptr(ring), int(ring_slots), _ptr(ws), ws.numel(), int(max_blocks), _stream()))
+
+
 def pack_weights_batched(layers):
   """layers: list of (w fp32 [k*cout], mask_bits|None, k, cout, hwio|None,
   ohwi|None)."""

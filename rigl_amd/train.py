@@ -84,6 +84,8 @@ class GradientDescentOptimizer(Optimizer):
     self._lr_step = None
     self._lr_dev = None
     self._lr_mirror = 0
+    # summaries.TrainingSummaries.attach() sets it: called once per apply, in front of the first update launch.  None: no launch
+    self._summary_hook = None
 
   # ---- gradients -------------------------------------------------------------
   def compute_gradients(self, loss, var_list=None, **kwargs):
@@ -176,6 +178,8 @@ class GradientDescentOptimizer(Optimizer):
       lr = _lr_value(self._lr, global_step)
     scale = self._grad_sync.grad_scale if self._grad_sync is not None else 1.0
     mu = float(self._momentum) if self._momentum is not None else 0.0
+    if self._summary_hook is not None:
+      self._summary_hook.on_apply(self, global_step, lr, scale)    # this step's record: the weights and gradients as they are now
     # one launch per segment; weight decay is uniform inside a kernel segment
     for kind in (V.KIND_MASKED, V.KIND_DENSE):
       b, e = g.seg[kind]
@@ -355,6 +359,7 @@ class GraphedStep:
     self._ws_gen = ops.WORKSPACE_GENERATION
     self._last_key = None      # learning-rate key of the previous ordinary step and how many steps it has been stable
     self._stable = 0
+    self._summ = getattr(inner, '_summary_hook', None)   # the summaries hook the cached graphs were captured with
     self._stable_needed = 1    # capture at the second consecutive ordinary step with the same learning rate
 
   def _is_update(self):
@@ -380,6 +385,14 @@ class GraphedStep:
       key = inner._lr                                              # pylint: disable=protected-access
     else:
       key = _lr_value(inner._lr, self._gs)                         # pylint: disable=protected-access
+    # attached training summaries keep a device step counter too, under the same protocol: a stale one is uploaded by an eager
+    # call, and graphs captured with another hook (or none) enqueue another set of launches
+    summ = getattr(inner, '_summary_hook', None)
+    if summ is not self._summ:
+      self._graphs.clear()
+      self._summ = summ
+    if summ is not None and _int32(self._gs.value) != summ.mirror:
+      return self._eager()
     if self._ws_gen != ops.WORKSPACE_GENERATION:
       # a scratch buffer was (re)allocated since the graphs were captured (an eager mask update outgrew one, typically):
       # EVERY cached graph may point at the old buffer -- drop them all and capture again.  Checked before every replay,
@@ -419,6 +432,8 @@ class GraphedStep:
       self._gs.value = step1
       if dev_lr:
         inner._advance_lr_mirror(-1)                               # pylint: disable=protected-access
+      if summ is not None:
+        summ.advance_mirror(-1)
       if gen0 != ops.WORKSPACE_GENERATION or gen0 != self._ws_gen:
         # a buffer grew during the pre-capture step or the capture itself: graphs cached under other learning rates are
         # stale, and this one may hold both addresses -- keep none, the next call captures on settled buffers
@@ -436,6 +451,8 @@ class GraphedStep:
     self._gs.value += 1
     if dev_lr:
       inner._advance_lr_mirror(1)                                  # pylint: disable=protected-access
-    self._inner.graph.shadows_dirty = True                         # the replayed update rewrote the weights
+    if summ is not None:
+      summ.advance_mirror(1)                                       # the replay wrote this step's record
+    self._inner.graph.shadows_dirty = True                        # the replayed update rewrote the weights
     self.replays += 1
     return loss

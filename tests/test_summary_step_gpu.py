@@ -1,0 +1,207 @@
+"""Training summaries inside a training step, eager and replayed.  The set-up of tests/test_graphed_schedule_gpu.py: WRN depth 10,
+width 1, batch 32, RigL with period 5, 25 calls (calls 0, 6, 12, 18 and 24 are mask updates: they apply nothing, advance no
+step and must leave no record).
+
+  (a) the record of a step matches tests/summary_ref.py on a snapshot of W, G and BITS taken between compute_gradients and
+      apply_gradients, within 2 * n * 2^-53 * S_ref; learning_rate is the rate the update used, bit for bit;
+  (b) eager and train.GraphedStep leave bit-identical records, one per applied global step, also behind global_step.assign;
+  (c) with and without summaries attached the run is bit-identical: weights, slots, masks, losses, global step;
+  (d) Adam, and DNW's dense undecayed update of the masked kernels, checked as in (a).
+"""
+import math
+
+import numpy as np
+import pytest
+
+import summary_ref as R
+
+torch = pytest.importorskip('torch')
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+BATCH = 32
+CALLS = 25
+F32 = np.float32
+
+
+def _schedule():
+  from rigl_amd import schedules as S
+  return S.imagenet_lr_schedule(0.4, BATCH, num_train_images=40, model_architecture='mobilenet_v1')
+
+
+def _run(mode, rate, attach=True, optimizer='momentum', method='rigl', calls=CALLS, snapshot=False, assign=None, warmup=2):
+  """mode 'eager' / 'graph'; rate 'device' (a schedules.Schedule on the device path) / 'float' (0.05)."""
+  from rigl_amd import sparse_optimizers as SO, sparse_utils, summaries, train, variables as V
+  from rigl_amd.workloads import wide_resnet
+  g = V.reset_default_graph(DEV)
+  model = wide_resnet.WideResNet(g, depth=10, width=1)
+  np.random.seed(0)
+  sparse_utils.get_mask_init_fn(g.get_masks(), 'erdos_renyi_kernel', 0.8, {})()
+  lr = 0.05 if rate == 'float' else _schedule()
+  if optimizer == 'adam':
+    inner = train.AdamOptimizer(lr if rate != 'float' else 0.001, graph=g)
+  else:
+    inner = train.MomentumOptimizer(lr, 0.9, use_nesterov=True, graph=g)
+  if method == 'rigl':
+    opt = SO.SparseRigLOptimizer(inner, 0, 1000, 5, drop_fraction=0.3, drop_fraction_anneal='cosine', noise_std=0.)
+  else:
+    opt = SO.SparseDNWOptimizer(inner, 0.8, 'erdos_renyi_kernel')
+  gs = g.get_or_create_global_step()
+  x, y = wide_resnet.synthetic_batch(BATCH, DEV)
+  loss_fn = lambda: model.loss(x, y)
+  summ = summaries.TrainingSummaries(g, opt, ring=64, steps_per_epoch=1.25).attach() if attach else None
+  st = train.GraphedStep(loss_fn, opt, gs, warmup=warmup) if mode == 'graph' else None
+  snaps, used_rates, losses, applied = {}, {}, [], []
+
+  def eager():
+    loss = loss_fn()
+    gv = opt.compute_gradients(loss)
+    if snapshot:
+      snaps[int(gs.value)] = (g.W.cpu().numpy().copy(), g.G.cpu().numpy().copy(), g.BITS.cpu().numpy().view(np.uint32).copy())
+    opt.apply_gradients(gv, global_step=gs)
+    return loss
+  run = st if st is not None else eager
+  for k in range(calls):
+    if assign is not None and k == assign[0]:
+      gs.assign(assign[1])
+    s0 = int(gs.value)
+    loss = float(run().detach().float())
+    losses.append(loss)
+    if int(gs.value) == s0 + 1:
+      applied.append((s0, loss))
+      used_rates[s0] = float(inner._lr_dev.cpu()[0]) if inner._lr_dev is not None else float(F32(inner._lr))
+  torch.cuda.synchronize()
+  out = dict(W=g.W.cpu().numpy().copy(), A=inner._slot.cpu().numpy().copy(), B=g.BITS.cpu().numpy().copy(), gs=int(gs.value),
+             losses=losses, applied=applied, rates=used_rates, snaps=snaps)
+  if optimizer == 'adam':
+    out['V'] = inner._slot_v.cpu().numpy().copy()
+  if st is not None:
+    out.update(replays=st.replays, n_graphs=len(st._graphs))
+  if summ is not None:
+    out['records'], out['dropped'] = summ.read(per_variable=True)
+    out['layout'] = summ.layout
+    out['mirror'], out['counter'] = summ.mirror, int(summ._step.cpu()[0])
+    out['variables'] = [(v.name, v.offset, v.numel, v.kind, v.weight_decay)
+                        for v in sorted(g.trainable_variables(), key=lambda v: v.offset)]
+    out['drop_fraction'] = {s: float(opt.get_drop_fraction(s, True)) for s, _ in applied} if method == 'rigl' else None
+  return out
+
+
+_RUNS = {}
+
+
+def _cached(*key, **kw):
+  k = key + tuple(sorted(kw.items()))
+  if k not in _RUNS:
+    _RUNS[k] = _run(*key, **kw)
+  return _RUNS[k]
+
+
+def _same_state(a, b):
+  np.testing.assert_array_equal(a['B'], b['B'])
+  for k in ('W', 'A') + (('V',) if 'V' in a else ()):
+    np.testing.assert_array_equal(a[k].view(np.uint32), b[k].view(np.uint32))
+  assert a['losses'] == b['losses'] and a['gs'] == b['gs']
+
+
+def _one_record_per_applied_step(out):
+  assert out['dropped'] == 0
+  assert [r['global_step'] for r in out['records']] == [s for s, _ in out['applied']]
+  assert out['mirror'] == out['counter'] == out['gs']
+
+
+def _against_snapshots(out, dnw=False):
+  layout = out['layout']
+  n_all = sum(l['n'] for l in layout)
+  assert [l['name'] for l in layout] == [v[0] for v in out['variables']]
+  assert sum(1 for l in layout if l['mask']) >= 3
+  for r, (s, loss) in zip(out['records'], out['applied']):
+    Wh, Gh, Bh = out['snaps'][s]
+    ref = []
+    for l, (name, off, n, kind, wd) in zip(layout, out['variables']):
+      masked = l['mask'] is not None
+      e = {'n': n, 'w_buf': Wh[off:], 'g_buf': Gh[off:], 'bits': Bh[off // 32:] if masked else None,
+           'weight_decay': 0.0 if (kind == 2 or (dnw and masked)) else wd, 'apply_mask': 0 if (dnw and masked) else 1}
+      ref.append(R.entry_sums(e, 1.0))
+    for k in R.COUNT_FIELDS:
+      assert [r['per_variable'][l['name']][k] for l in layout] == [e[k] for e in ref], (s, k)
+    for k in R.FLOAT_FIELDS:
+      for l, e in zip(layout, ref):
+        got = r['per_variable'][l['name']][k]
+        assert R.float_ok(got, e[k], l['n']), (s, k, l['name'], got, e[k])
+    sg, sw = math.fsum(e['sumsq_g'] for e in ref), math.fsum(e['sumsq_w'] for e in ref)
+    assert sg > 0 and abs(r['grad_norm'] ** 2 - sg) <= R.bound(n_all, sg) + 4 * 2.0 ** -53 * sg   # (+ the root, squared again)
+    assert abs(r['var_norm'] ** 2 - sw) <= R.bound(n_all, sw) + 4 * 2.0 ** -53 * sw
+    assert r['learning_rate'] == out['rates'][s]                       # the rate the update read, bit for bit
+    assert r['cross_loss'] == loss                                     # the loss that was backpropagated
+    reg = sum(wd * e['sumsq_w'] / 2.0 for e, (_, _, _, _, wd) in zip(ref, out['variables']) if wd > 0.0)
+    assert abs(r['reg_loss'] - reg) <= 1e-12 * reg and r['loss'] == r['cross_loss'] + r['reg_loss']
+    assert r['current_epoch'] == s / 1.25 and r['grad_nonfinite'] == 0
+    masked = [(l, e) for l, e in zip(layout, ref) if l['mask']]
+    ones, dense = sum(e['mask_ones'] for _, e in masked), sum(l['n'] for l, _ in masked)
+    assert r['global_sparsity'] == 1. - float(ones) / float(dense)
+    assert r['fw_nz_mask'] == masked[0][1]['mask_ones'] and r['fw_nz_weight'] == masked[0][1]['nz_w']
+    for l, e in masked:
+      key = 'pruning/%s/sparsity' % l['mask'][:-2]
+      assert r[key] == float(F32(1) - F32(F32(e['mask_ones']) / F32(l['n'])))
+    if out['drop_fraction'] is not None:
+      assert r['drop_fraction'] == out['drop_fraction'][s]
+    else:
+      assert 'drop_fraction' not in r
+
+
+def test_a_eager_records_match_the_reference_on_snapshots():
+  out = _cached('eager', 'device', snapshot=True)
+  assert out['gs'] == CALLS - 5 and len(out['applied']) == CALLS - 5
+  _one_record_per_applied_step(out)
+  _against_snapshots(out)
+  sched = _schedule()
+  assert [r['learning_rate'] for r in out['records']] == [sched(s) for s, _ in out['applied']]
+  # the dense gradient arena is NOT what is logged: the masked kernels' dense gradient is larger than the applied one
+  Wh, Gh, _ = out['snaps'][3]
+  assert float(np.sqrt(np.sum(Gh.astype(np.float64) ** 2))) > 1.05 * out['records'][3]['grad_norm']
+
+
+@pytest.mark.parametrize('rate', ['device', 'float'])
+def test_b_eager_and_graphed_step_leave_the_same_records(rate):
+  a = _cached('eager', rate, snapshot=(rate == 'device'))
+  c = _cached('graph', rate)
+  _same_state(a, c)
+  assert c['replays'] >= 8 and c['n_graphs'] == 1
+  _one_record_per_applied_step(a)
+  _one_record_per_applied_step(c)
+  assert a['records'] == c['records']                                   # every key, every per-variable sum: the same bits
+  assert all(math.isfinite(r['grad_norm']) and r['grad_norm'] > 0 for r in c['records'])
+
+
+def test_b_assigning_the_global_step_carries_into_the_next_record():
+  a = _cached('eager', 'device', assign=(10, 40))
+  c = _cached('graph', 'device', assign=(10, 40))
+  _same_state(a, c)
+  _one_record_per_applied_step(c)
+  steps = [r['global_step'] for r in c['records']]
+  assert 40 in steps and steps[steps.index(40) - 1] == 7 and steps[-1] == c['gs'] - 1 > 50
+  assert a['records'] == c['records'] and c['replays'] >= 8 and c['n_graphs'] == 1
+
+
+@pytest.mark.parametrize('mode', ['eager', 'graph'])
+def test_c_attaching_changes_nothing(mode):
+  with_s = _cached(mode, 'device', snapshot=(mode == 'eager'))
+  without = _cached(mode, 'device', attach=False)
+  _same_state(with_s, without)
+  if mode == 'graph':
+    assert with_s['replays'] == without['replays']
+
+
+def test_d_adam():
+  out = _cached('eager', 'device', optimizer='adam', calls=8, snapshot=True)
+  _one_record_per_applied_step(out)
+  assert len(out['records']) == 6
+  _against_snapshots(out)
+
+
+def test_d_dnw_logs_the_dense_undecayed_gradient_of_masked_kernels():
+  out = _cached('eager', 'float', method='dnw', calls=4, snapshot=True)
+  _one_record_per_applied_step(out)
+  assert len(out['records']) == 4
+  _against_snapshots(out, dnw=True)
