@@ -480,6 +480,44 @@ int rigl_summary_step(const RiglSummaryEntry* entries /* host */, int32_t n_entr
                       int32_t ring_slots, void* workspace, size_t workspace_size /* bytes */,
                       int32_t max_blocks, rigl_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Micro-batch gradient accumulation: k forward/backward passes, one update.
+ *   Replaces: the cross-replica sum of every variable gradient at a global
+ *   batch of k x the per-core batch (rigl/imagenet_resnet/
+ *   imagenet_train_eval.py:363-365, rigl/sparse_optimizers_base.py:472-473),
+ *   serialised onto one GPU: the wgrad kernels overwrite their slice of the
+ *   gradient arena, so the running sum lives in a second arena and ONE
+ *   launch over the whole arena per micro-batch moves it on:
+ *     FIRST: acc = g           loss_acc = loss
+ *     ADD  : acc = acc + g     loss_acc = loss_acc + loss
+ *     LAST : g   = acc + g     loss_mean = (loss_acc + loss) * inv_k
+ *   FIRST is a copy (bit for bit, NaN payloads included): no memset, and a
+ *   stale acc never reaches a step.  LAST leaves the raw SUM in the gradient
+ *   arena, where every consumer reads it; acc and loss_acc are only read.
+ * Arithmetic: one IEEE fp32 addition per element (round to nearest even, no
+ * FMA, no wider intermediate, no atomics); subnormals are kept, signed zeros,
+ * infinities and NaN follow IEEE.  The result bits depend on the operands
+ * alone, not on the grid or max_blocks.  The loss scalar is handled by one
+ * lane of the same launch; its addition and the product with inv_k are
+ * rounded to fp32 separately.  loss == NULL: no loss arithmetic at all.
+ * acc and grad are distinct 16-byte aligned buffers of n >= 0 fp32; no
+ * element at or beyond n is touched (the n % 4 tail is handled).  n == 0 with
+ * a loss still does the loss arithmetic.  max_blocks caps the grid (0 = the
+ * default, 8 blocks per CU).
+ * RIGL_EINVAL, with nothing launched or written: a NULL or misaligned acc /
+ * grad (or acc == grad), an unknown mode, n < 0, max_blocks < 0, loss without
+ * loss_acc, LAST with loss but no loss_mean, a loss pointer that is not
+ * 4-byte aligned.
+ * ---------------------------------------------------------------------- */
+#define RIGL_ACC_FIRST 0
+#define RIGL_ACC_ADD 1
+#define RIGL_ACC_LAST 2
+int rigl_grad_accumulate(int64_t n, float* acc, float* grad, int32_t mode,
+                         const float* loss /* device [1], nullable */,
+                         float* loss_acc /* device [1] */,
+                         float* loss_mean /* device [1], written in LAST only */,
+                         float inv_k, int32_t max_blocks, rigl_stream_t stream);
+
 /* bf16 shadows of mask*W for the conv kernels:  hwio[i] = bf16(mask_i?w_i:0)
  * in flat HWIO order (dgrad operand) and ohwi = the [cout][kh*kw*cin]
  * transpose (fwd operand).  Either output may be NULL.  k = kh*kw*cin.      */

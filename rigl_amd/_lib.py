@@ -109,6 +109,10 @@ SUMMARY_HEADER_BYTES = 16     # int32 step, int32 n_entries, fp32 loss, fp32 lea
 SUMMARY_GROUP_BYTES = 48      # 3 fp64 (sumsq_g, sumsq_w, l1_w), 3 int64 (nz_w, mask_ones, nonfinite_g): the totals, then every entry
 
 
+ACC_FIRST, ACC_ADD, ACC_LAST = 0, 1, 2   # RIGL_ACC_*: the modes of rigl_grad_accumulate
+ACC_TILE = 4096               # elements per block and iteration of rigl_grad_accumulate (256 lanes x 4 float4)
+
+
 class SummaryEntry(C.Structure):
   """RiglSummaryEntry: one trainable variable of rigl_summary_step."""
   _fields_ = [('n', C.c_int64), ('w', C.c_void_p), ('g', C.c_void_p), ('mask_bits', C.c_void_p),
@@ -152,6 +156,7 @@ SIGNATURES = {
     'rigl_summary_slot_bytes': (_SZ, [_I32]),
     'rigl_summary_workspace_bytes': (_SZ, [C.POINTER(SummaryEntry), _I32]),
     'rigl_summary_step': (C.c_int, [C.POINTER(SummaryEntry), _I32, _F, _P, _P, _F, _P, _P, _I32, _P, _SZ, _I32, _P]),
+    'rigl_grad_accumulate': (C.c_int, [_I64, _P, _P, _I32, _P, _P, _P, _F, _I32, _P]),
     'rigl_pack_weights': (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
     'rigl_pack_weights_batched': (C.c_int, [C.POINTER(PackLayer), _I32, _P]),
     'rigl_conv2d_workspace_bytes': (_SZ, [C.POINTER(ConvDesc), _I32]),

@@ -398,6 +398,25 @@ def summary_step(table, step, ring, ring_slots, grad_scale=1.0, loss=None, lr=No
                               _ptr(step), _ptr(ring), int(ring_slots), _ptr(ws), ws.numel(), int(max_blocks), _stream()))
 
 
+def grad_accumulate(acc, grad, mode, loss=None, loss_acc=None, loss_mean=None, inv_k=1.0, max_blocks=0):
+  """One pass of micro-batch gradient accumulation over two fp32 arenas of one size (rigl_grad_accumulate).  ``mode``:
+  _lib.ACC_FIRST ``acc = grad``, ACC_ADD ``acc += grad``, ACC_LAST ``grad = acc + grad`` (acc is only read).  ``loss`` (fp32 [1]
+  on the GPU, or None: no loss arithmetic): FIRST ``loss_acc = loss``, ADD ``loss_acc += loss``, LAST ``loss_mean =
+  (loss_acc + loss) * inv_k``.  One launch, capture-safe."""
+  _req(acc, torch.float32, 'acc')
+  _req(grad, torch.float32, 'grad')
+  _req(loss, torch.float32, 'loss', allow_none=True)
+  _req(loss_acc, torch.float32, 'loss_acc', allow_none=True)
+  _req(loss_mean, torch.float32, 'loss_mean', allow_none=True)
+  if acc.numel() != grad.numel():
+    raise ValueError('size mismatch: acc has %d elements, grad %d' % (acc.numel(), grad.numel()))
+  for t, name in ((loss, 'loss'), (loss_acc, 'loss_acc'), (loss_mean, 'loss_mean')):
+    if t is not None and t.numel() != 1:
+      raise ValueError('%s must hold 1 float' % name)
+  check(_lib.load().rigl_grad_accumulate(acc.numel(), _ptr(acc), _ptr(grad), int(mode), _ptr(loss), _ptr(loss_acc),
+                                         _ptr(loss_mean), float(inv_k), int(max_blocks), _stream()))
+
+
 def pack_weights_batched(layers):
   """layers: list of (w fp32 [k*cout], mask_bits|None, k, cout, hwio|None,
   ohwi|None)."""

@@ -620,6 +620,8 @@ class SparseSnipOptimizer(PruningGetterMixin, train.Optimizer):
         g_var = l.weights.grad
         sync = getattr(self._optimizer, '_grad_sync', None)
         scale = float(getattr(sync, 'grad_scale', 1.0)) if sync is not None else 1.0
+        if hasattr(self._optimizer, 'update_scale'):
+          scale = float(self._optimizer.update_scale())   # ... and the 1 / k of a train.MicroBatches sum, likewise
         if scale != 1.0:
           g_var = g_var * scale
         if l.weights.weight_decay:

@@ -262,6 +262,9 @@ class TrainingSummaries:
         self._step.fill_(want)
         self.mirror = want
     loss = inner._backward_done_for                   # pylint: disable=protected-access
+    acc = getattr(inner, '_accum', None)
+    if acc is not None and acc.covers(loss):
+      loss = acc.loss                                 # train.MicroBatches: the mean over the step's micro-batches, not the last one's
     if not (torch.is_tensor(loss) and loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
       loss = None
     ops.summary_step(self._tables[bool(inner.dense_masked_update)], self._step, self._ring, self._ledger.slots,

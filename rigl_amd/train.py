@@ -23,6 +23,7 @@ kernels read the rate through a pointer -- so ``GraphedStep`` replays one graph 
 """
 import torch
 
+from rigl_amd import _lib
 from rigl_amd import ops
 from rigl_amd import schedules
 from rigl_amd import variables as V
@@ -86,6 +87,8 @@ class GradientDescentOptimizer(Optimizer):
     self._lr_mirror = 0
     # summaries.TrainingSummaries.attach() sets it: called once per apply, in front of the first update launch.  None: no launch
     self._summary_hook = None
+    # the MicroBatches whose sum is pending or finished for the loss being minimised (set by its call), or None
+    self._accum = None
 
   # ---- gradients -------------------------------------------------------------
   def compute_gradients(self, loss, var_list=None, **kwargs):
@@ -95,10 +98,15 @@ class GradientDescentOptimizer(Optimizer):
     del kwargs
     g = self.graph
     g.finalize()
+    acc = self._accum
+    if acc is not None and loss is not None:
+      acc.check_pending(loss)      # a sum pending for another loss: refused, never guessed
     if loss is not None and self._backward_done_for is not loss:
       g.zero_other_grads()
       loss.backward()
       self._backward_done_for = loss
+      if acc is not None:
+        acc.finish(loss)           # the LAST pass of a pending sum: the arena holds the raw sum before anything reads it
       if self._grad_sync is not None:
         self._grad_sync.all_reduce(g)
     if var_list is not None:
@@ -108,6 +116,16 @@ class GradientDescentOptimizer(Optimizer):
     return self._last_gv
 
   # ---- update ----------------------------------------------------------------
+  def update_scale(self):
+    """The factor the update kernels (momentum and Adam alike) and the summaries apply to the arena's gradient: the 1 / world
+    of a GradSync, whose all-reduce leaves the sum over replicas, times the 1 / k of a MicroBatches accumulation finished for
+    the loss that was backpropagated, which leaves the sum over micro-batches."""
+    scale = self._grad_sync.grad_scale if self._grad_sync is not None else 1.0
+    acc = self._accum
+    if acc is not None and acc.finished_for(self._backward_done_for):
+      scale = scale * acc.inv_k
+    return scale
+
   def _ensure_slots(self):
     self._ensure_lr_buffers()
 
@@ -176,7 +194,7 @@ class GradientDescentOptimizer(Optimizer):
       lr = None                      # the update launches read self._lr_dev
     else:
       lr = _lr_value(self._lr, global_step)
-    scale = self._grad_sync.grad_scale if self._grad_sync is not None else 1.0
+    scale = self.update_scale()
     mu = float(self._momentum) if self._momentum is not None else 0.0
     if self._summary_hook is not None:
       self._summary_hook.on_apply(self, global_step, lr, scale)    # this step's record: the weights and gradients as they are now
@@ -201,6 +219,8 @@ class GradientDescentOptimizer(Optimizer):
     self._finish()
     g.shadows_dirty = True
     self._backward_done_for = None
+    if self._accum is not None:
+      self._accum.release()
     if global_step is not None:
       global_step.value += 1
     return None
@@ -319,6 +339,137 @@ class AdamOptimizer(GradientDescentOptimizer):
     ops.adam_advance(self._beta_powers, self._beta1, self._beta2)
 
 
+class MicroBatches:
+  """k micro-batches, one optimizer step: a k-replica run of the reference (per-core batch, gradients summed over cores,
+  imagenet_train_eval.py:363-365) serialised onto one GPU.
+
+    mb = MicroBatches(loss_fn, optimizer, micro_batches=k)   # a callable with loss_fn's signature
+    optimizer.minimize(mb(), gs)                             # eager
+    step = GraphedStep(mb, optimizer, gs)                    # one captured graph = k passes + one update
+    mb.loss                                                  # device fp32 [1]: mean of the step's k micro-batch losses
+
+  ``optimizer``: an inner optimizer of this module or a wrapper around one (its ``_optimizer``).  ``mb()`` runs micro-batches
+  1..k-1 itself -- loss_fn(), zero_other_grads(), backward(), one ops.grad_accumulate pass over the whole gradient arena (FIRST,
+  then ADD) into a second arena -- calls loss_fn() a k-th time and returns THAT loss, with the sum pending against it.  The
+  inner optimizer's compute_gradients backpropagates it as always and then enqueues the LAST pass, once and in front of every
+  reader: the arena holds the raw fp32 SUM fl(fl(g1+g2)+g3)..., which is what RigL's grow scores, DNW, pruning and the
+  summaries read (the reference's cross-replica sum, sparse_optimizers_base.py:472-473), and the mean is folded into the
+  update's grad_scale (update_scale).  compute_gradients on another loss while a sum is pending raises.
+
+  Once per call, i.e. per optimizer step: the global step, the learning-rate counter, the summaries record (its loss is
+  ``mb.loss``), the mask-update schedule, weight decay and the Adam beta powers.  Once per micro-batch: batch-norm batch
+  statistics and moving-average updates, dropout draws, DeviceCifar.next_batch() -- k consecutive forward passes, like k
+  replicas.  A mask-update call runs its k micro-batches too and hands the mask update the raw sum.
+
+  With k == 1 ``mb()`` is ``loss_fn()``: no pass is enqueued, no buffer is allocated, no scale changes.  Every launch goes
+  into whatever is being captured and every buffer (the second arena, the loss accumulator and mean) is allocated here, so
+  GraphedStep(mb, ...) captures and replays the k passes and the update as one graph.
+
+  Not combined with data parallelism yet: an enabled GradSync (world > 1) raises NotImplementedError -- its bucket exchange
+  starts inside every backward pass and would have to be held back to the last micro-batch; that is a follow-up."""
+
+  def __init__(self, loss_fn, optimizer, micro_batches):
+    k = int(micro_batches)
+    if k < 1 or k != micro_batches:
+      raise ValueError('micro_batches must be an integer >= 1, got %r' % (micro_batches,))
+    inner = getattr(optimizer, '_optimizer', optimizer)
+    if not hasattr(inner, '_accum'):
+      raise TypeError('%s cannot accumulate (expected a rigl_amd.train optimizer or a wrapper around one)' % type(inner).__name__)
+    sync = getattr(inner, '_grad_sync', None)
+    if sync is not None and getattr(sync, 'enabled', False):
+      raise NotImplementedError('MicroBatches with an enabled GradSync (world > 1): accumulation is not combined with the '
+                                'in-backward bucket exchange yet')
+    self._loss_fn = loss_fn
+    self._inner = inner
+    self.micro_batches = k
+    self.inv_k = 1.0 / k
+    self._pending = None           # the k-th loss, between __call__ and the compute_gradients that backpropagates it
+    self._done_for = None          # the loss whose LAST pass was enqueued: the arena holds its sum
+    self._last = None              # k == 1: the loss of the last call
+    self._arena = self._loss_acc = self._loss_mean = None
+    if k > 1:
+      g = inner.graph
+      g.finalize()
+      if g.W is None or not g.W.is_cuda:
+        raise _lib.RiglError(_lib.RIGL_EINVAL, 'MicroBatches needs a graph on the GPU (no CPU path exists)')
+      self._build()
+      g.add_relayout_callback(self._build)
+
+  def _build(self):
+    """(Re)allocates the second arena with the layout of G, and the two loss scalars."""
+    G = self._inner.graph.G
+    self._arena = torch.empty_like(G)       # FIRST overwrites all of it: never read before it is written
+    self._loss_acc = torch.zeros(1, dtype=torch.float32, device=G.device)
+    self._loss_mean = torch.zeros(1, dtype=torch.float32, device=G.device)
+    self._pending = self._done_for = None
+
+  @property
+  def loss(self):
+    """Device fp32 [1]: the mean of the k micro-batch losses of the last step whose gradients were computed."""
+    if self.micro_batches == 1:
+      return None if self._last is None else self._last.reshape(1)
+    return self._loss_mean
+
+  @staticmethod
+  def _check_loss(loss):
+    if not (torch.is_tensor(loss) and loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
+      raise TypeError('MicroBatches: loss_fn must return one fp32 scalar on the GPU')
+    return loss.detach()
+
+  def __call__(self, *args, **kwargs):
+    if self.micro_batches == 1:
+      loss = self._loss_fn(*args, **kwargs)
+      self._last = loss.detach() if torch.is_tensor(loss) else None   # (an alias of the value, not of the autograd graph)
+      return loss
+    inner = self._inner
+    g = inner.graph
+    g.finalize()
+    # A new step begins: nothing of the last one is kept.  A loss tensor that stays referenced keeps its autograd graph's
+    # AccumulateGrad nodes of the bias / batch-norm leaves alive, the next forward pass reuses them, and they run on the
+    # stream they were created on -- for ever the stream of the first step.  A step captured on another stream would pull
+    # that stream into its capture.  So the references taken here live from this call to the apply (or the next call).
+    self._pending = self._done_for = None
+    inner._backward_done_for = None                     # pylint: disable=protected-access
+    for i in range(self.micro_batches - 1):
+      loss = self._loss_fn(*args, **kwargs)
+      scalar = self._check_loss(loss)
+      g.zero_other_grads()
+      loss.backward()
+      ops.grad_accumulate(self._arena, g.G, _lib.ACC_FIRST if i == 0 else _lib.ACC_ADD,
+                          loss=scalar, loss_acc=self._loss_acc)
+      del loss, scalar
+    loss = self._loss_fn(*args, **kwargs)
+    self._check_loss(loss)
+    self._pending = loss
+    inner._accum = self                                 # pylint: disable=protected-access
+    return loss
+
+  # ---- the inner optimizer's side ------------------------------------------------------------------------------------------
+  def check_pending(self, loss):
+    if self._pending is not None and self._pending is not loss:
+      raise RuntimeError('compute_gradients on another loss while the sum of %d micro-batches is pending: pass the tensor '
+                         'MicroBatches.__call__ returned' % (self.micro_batches - 1))
+
+  def finish(self, loss):
+    """Behind the backward pass of ``loss``: the LAST pass, when the sum is pending for exactly this tensor."""
+    if self._pending is None or self._pending is not loss:
+      return
+    ops.grad_accumulate(self._arena, self._inner.graph.G, _lib.ACC_LAST, loss=loss.detach(),
+                        loss_acc=self._loss_acc, loss_mean=self._loss_mean, inv_k=self.inv_k)
+    self._pending, self._done_for = None, loss
+
+  def finished_for(self, loss):
+    return loss is not None and self._done_for is loss
+
+  def release(self):
+    """The update was applied: the step's loss is let go of (see __call__)."""
+    self._done_for = None
+
+  def covers(self, loss):
+    """True when ``loss`` has a pending or finished accumulation: its record's loss is ``self.loss``."""
+    return loss is not None and (self._pending is loss or self._done_for is loss)
+
+
 class GraphedStep:
   """One training step replayed from a captured HIP graph (torch.cuda.CUDAGraph over the kernels the
   C ABI enqueues on the current stream) -- for launch-bound models, where the ~250 launches of a step cost
@@ -340,7 +491,8 @@ class GraphedStep:
   (``global_step.assign``, a checkpoint restore) the call runs eagerly, which uploads the counter -- a graph is
   never replayed against a stale counter.  The loss tensor returned is the captured step's output buffer.
 
-  ``loss_fn`` must read its inputs from fixed device buffers (copy each new batch into them).  Data-parallel
+  ``loss_fn`` must read its inputs from fixed device buffers (copy each new batch into them); a ``MicroBatches`` as ``loss_fn``
+  puts its k forward / backward passes and the one update into the same graph.  Data-parallel
   steps (a GradSync with world > 1) are not captured -- the collectives stay eager -- and run as usual.
   """
 
