@@ -776,7 +776,10 @@ int rigl_depthwise_conv2d_wgrad(const RiglConvDesc* d, const rigl_bf16* x,
 /* Direct (non-MFMA) kernels, same operand layouts, any channel count: taken
  * for shapes the MFMA path reports RIGL_EUNSUPPORTED for (cin/cout not a
  * multiple of 8 -- MNIST MLP 784-300-100-10, 10-class logits) and used as an
- * independent on-device cross-check.                                        */
+ * independent on-device cross-check.  They validate the descriptor as the
+ * MFMA entry points do (RIGL_EINVAL: a non-positive dimension, an output grid
+ * inconsistent with input / stride / pad; RIGL_EUNSUPPORTED: a tensor of 2^30
+ * elements or more) before a pointer is used or anything is launched.       */
 int rigl_conv2d_fwd_ref(const RiglConvDesc* d, const rigl_bf16* x,
                         const rigl_bf16* w_ohwi, rigl_bf16* y,
                         rigl_stream_t stream);

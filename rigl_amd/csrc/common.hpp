@@ -82,6 +82,24 @@ inline void prof_launch(F kernel, dim3 grid, dim3 blk, unsigned lds, hipStream_t
     else hipLaunchKernelGGL(kernel, grid, blk, lds, st, __VA_ARGS__);                       \
   } while (0)
 
+// What every K1 entry point asks of a conv descriptor before it touches a pointer (conv.hip's bodies and the direct kernels
+// of conv_ref.hip alike): positive dimensions, an output grid whose windows start inside the padded image, tensors below
+// 2^30 elements.
+inline int check_desc(const RiglConvDesc* d, const char* who) {
+  if (!d) return fail(RIGL_EINVAL, "%s: NULL descriptor", who);
+  if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->ho <= 0 || d->wo <= 0 || d->cout <= 0 || d->kh <= 0 ||
+      d->kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_top < 0 || d->pad_left < 0)
+    return fail(RIGL_EINVAL, "%s: non-positive dimension in descriptor", who);
+  // every output pixel's window must start inside the padded image
+  if ((d->ho - 1) * d->stride_h - d->pad_top >= d->h || (d->wo - 1) * d->stride_w - d->pad_left >= d->w)
+    return fail(RIGL_EINVAL, "%s: output size inconsistent with input/stride/pad", who);
+  const int64_t lim = (int64_t(1) << 30) - 1;   // bf16 tensors stay below 2^31 bytes (buffer descriptors)
+  if ((int64_t)d->n * d->h * d->w * d->cin > lim || (int64_t)d->n * d->ho * d->wo * d->cout > lim ||
+      (int64_t)d->kh * d->kw * d->cin * d->cout > lim)
+    return fail(RIGL_EUNSUPPORTED, "%s: tensor exceeds 2^30 elements", who);
+  return RIGL_OK;
+}
+
 inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -1388,21 +1388,7 @@ static void launch_igemm(const IgemmArgs& a0, hipStream_t st) {
   else launch_igemm_t<MODE, F32, false, EPI>(a, dim3(pl.grid), pl.wide_n, pl.dma, st);
 }
 
-static int check_desc(const RiglConvDesc* d, const char* who) {
-  if (!d) return fail(RIGL_EINVAL, "%s: NULL descriptor", who);
-  if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->ho <= 0 || d->wo <= 0 || d->cout <= 0 || d->kh <= 0 ||
-      d->kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_top < 0 || d->pad_left < 0)
-    return fail(RIGL_EINVAL, "%s: non-positive dimension in descriptor", who);
-  // every output pixel's window must start inside the padded image
-  if ((d->ho - 1) * d->stride_h - d->pad_top >= d->h || (d->wo - 1) * d->stride_w - d->pad_left >= d->w)
-    return fail(RIGL_EINVAL, "%s: output size inconsistent with input/stride/pad", who);
-  const int64_t lim = (int64_t(1) << 30) - 1;   // bf16 tensors stay below 2^31 bytes (buffer descriptors)
-  if ((int64_t)d->n * d->h * d->w * d->cin > lim || (int64_t)d->n * d->ho * d->wo * d->cout > lim ||
-      (int64_t)d->kh * d->kw * d->cin * d->cout > lim)
-    return fail(RIGL_EUNSUPPORTED, "%s: tensor exceeds 2^30 elements", who);
-  return RIGL_OK;
-}
-
+// (check_desc: common.hpp -- the direct kernels of conv_ref.hip validate their descriptors with the same function)
 static inline bool small_cin(const RiglConvDesc* d) { return (d->cin % 8) != 0 && d->cin > 4; }
 static inline int kpad(const RiglConvDesc* d) { return (d->kh * d->kw * d->cin + 31) / 32 * 32; }
 

@@ -116,7 +116,9 @@ extern "C" {
 int rigl_conv2d_fwd_ref(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* w_ohwi, rigl_bf16* y,
                         rigl_stream_t stream) {
   using namespace rigl;
-  if (!d || !x || !w_ohwi || !y) return fail(RIGL_EINVAL, "rigl_conv2d_fwd_ref: NULL argument");
+  int rc = check_desc(d, "rigl_conv2d_fwd_ref");
+  if (rc) return rc;
+  if (!x || !w_ohwi || !y) return fail(RIGL_EINVAL, "rigl_conv2d_fwd_ref: NULL argument");
   hipStream_t st = as_stream(stream);
   ProfScope prof(PROF_CONV_FWD, st);
   hipLaunchKernelGGL(kref::k_fwd, dim3(kref::grid_for((int64_t)d->n * d->ho * d->wo * d->cout)), dim3(kref::THREADS), 0,
@@ -128,7 +130,9 @@ int rigl_conv2d_fwd_ref(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf
 int rigl_conv2d_dgrad_ref(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio, rigl_bf16* dx,
                           rigl_stream_t stream) {
   using namespace rigl;
-  if (!d || !dy || !w_hwio || !dx) return fail(RIGL_EINVAL, "rigl_conv2d_dgrad_ref: NULL argument");
+  int rc = check_desc(d, "rigl_conv2d_dgrad_ref");
+  if (rc) return rc;
+  if (!dy || !w_hwio || !dx) return fail(RIGL_EINVAL, "rigl_conv2d_dgrad_ref: NULL argument");
   hipStream_t st = as_stream(stream);
   ProfScope prof(PROF_CONV_DGRAD, st);
   hipLaunchKernelGGL(kref::k_dgrad, dim3(kref::grid_for((int64_t)d->n * d->h * d->w * d->cin)), dim3(kref::THREADS), 0,
@@ -140,7 +144,9 @@ int rigl_conv2d_dgrad_ref(const RiglConvDesc* d, const rigl_bf16* dy, const rigl
 int rigl_conv2d_wgrad_ref(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, float* dw,
                           rigl_stream_t stream) {
   using namespace rigl;
-  if (!d || !x || !dy || !dw) return fail(RIGL_EINVAL, "rigl_conv2d_wgrad_ref: NULL argument");
+  int rc = check_desc(d, "rigl_conv2d_wgrad_ref");
+  if (rc) return rc;
+  if (!x || !dy || !dw) return fail(RIGL_EINVAL, "rigl_conv2d_wgrad_ref: NULL argument");
   hipStream_t st = as_stream(stream);
   ProfScope prof(PROF_CONV_WGRAD, st);
   hipLaunchKernelGGL(kref::k_wgrad, dim3(kref::grid_for((int64_t)d->kh * d->kw * d->cin * d->cout)), dim3(kref::THREADS),

@@ -125,6 +125,50 @@ BS_CASES = [
 ]
 
 
+# The small-channel layers (tests/k1_exact.py --set wrn | mlp | odd: the exact runner only; these lists are not walked by
+# run_case below, whose dX checks stop at cin % 8 != 0).
+# WideResNet-22, widths 1 and 2, on a 32 x 32 input: the 16 / 32 / 64-channel 3x3 layers, the stride-2 3x3 layers with TF SAME
+# (0, 1) padding on 32 -> 16 and 16 -> 8, the 1x1 stride-2 VALID skips, the 3 -> 16 stem (the 64 -> 10 logits: MLP_CASES)
+WRN_CASES = [
+    (3, 32, 32, 3, 16, 3, 1, 1, 1, 32, 32),        # the stem: tiny Cin on the padded-to-4 path, 16 output columns
+    (3, 32, 32, 16, 16, 3, 1, 1, 1, 32, 32),       # conv_2: 16 -> 16, one 16-channel K block per tap
+    (3, 32, 32, 16, 32, 3, 2, 0, 0, 16, 16),       # conv_3's first 3x3: stride 2, TF SAME on an even size (pad 0 / 1)
+    (3, 32, 32, 16, 32, 1, 2, 0, 0, 16, 16),       # its 1x1 stride-2 VALID skip (dX on its own grid)
+    (3, 16, 16, 32, 32, 3, 1, 1, 1, 16, 16),       # conv_3: 32 -> 32
+    (3, 16, 16, 32, 64, 3, 2, 0, 0, 8, 8),         # conv_4's first 3x3: 16 -> 8
+    (3, 16, 16, 32, 64, 1, 2, 0, 0, 8, 8),         # its skip
+    (5, 8, 8, 64, 64, 3, 1, 1, 1, 8, 8),           # conv_4: 64 -> 64 on 8 x 8 (too narrow for the slab-resident 3x3)
+    (3, 32, 32, 16, 32, 1, 1, 0, 0, 32, 32),       # width 2: the stride-1 skip of conv_2
+    (3, 8, 8, 128, 128, 3, 1, 1, 1, 8, 8),         # width 2: conv_4, 128 -> 128
+]
+
+# Dense layers and classifier heads as the 1x1 convs they run as: cout % 8 != 0 sends a layer to the direct kernels of
+# conv_ref.hip (fwd, dgrad and wgrad), cin % 8 != 0 with cout % 8 == 0 would send only its dgrad there
+MLP_CASES = [
+    (100, 1, 1, 784, 300, 1, 1, 0, 0, 1, 1),       # MNIST MLP layer 1
+    (100, 1, 1, 300, 100, 1, 1, 0, 0, 1, 1),       # layer 2: neither channel count a multiple of 8
+    (100, 1, 1, 100, 10, 1, 1, 0, 0, 1, 1),        # layer 3
+    (128, 1, 1, 64, 10, 1, 1, 0, 0, 1, 1),         # WideResNet-22's logits (width 1)
+    (37, 1, 1, 128, 10, 1, 1, 0, 0, 1, 1),         # ... width 2, a ragged batch
+    (8, 1, 1, 2048, 1000, 1, 1, 0, 0, 1, 1),       # an ImageNet head: cout % 8 == 0, eight rows
+]
+
+# The ragged shapes of test_k3_k1_gpu.CONV_CASES, and cout % 8 != 0 with 3x3 and stride 2: the explicit im2col path
+# (cin % 8 != 0, cin > 4), tiny Cin with 3x3 / 5x5, the host fallbacks of conv_bwd / conv_dgrad
+ODD_CASES = [
+    (2, 9, 11, 16, 48, 3, 1, 1, 1, 9, 11),         # H != W, odd sizes, 48 columns
+    (2, 10, 10, 40, 72, 3, 1, 1, 1, 10, 10),       # 40 -> 72: a ragged K block and ragged columns
+    (2, 15, 13, 16, 32, 3, 2, 1, 1, 8, 7),         # stride 2 with fixed padding 1 on odd sizes
+    (3, 20, 20, 24, 40, 1, 2, 0, 0, 10, 10),       # strided 1x1, 24 -> 40
+    (2, 17, 19, 3, 32, 3, 2, 0, 0, 9, 10),         # tiny Cin, stride 2, windows that hang two rows over the bottom edge
+    (2, 12, 12, 4, 16, 5, 1, 2, 2, 12, 12),        # Cin = 4 (the tiny path's full pixel), 5x5
+    (2, 10, 10, 15, 24, 3, 1, 1, 1, 10, 10),       # im2col: K = 135 padded to 160; dX from the direct kernel
+    (3, 9, 11, 20, 40, 3, 1, 1, 1, 9, 11),         # im2col: K = 180 padded to 192
+    (2, 10, 10, 15, 21, 3, 1, 1, 1, 10, 10),       # neither a multiple of 8: all three direct kernels, 3x3
+    (2, 7, 9, 12, 10, 3, 2, 0, 0, 4, 5),           # ... with stride 2 and windows over the bottom / right edge
+]
+
+
 def _c3_tile_rows(H, W):
   """Tile height of the c3x3.hpp forward (c3x3_geom restated): the most rows whose patch + zero tail fit the 544-pixel
   LDS budget of one of the two patch buffers, one fewer where that divides H."""

@@ -8,7 +8,15 @@ are small integers times a power-of-two unit with sum|a||b| <= 2^24 units, so fp
 the expected BITS follow from tests/convref.py's fp64 result and the one documented final rounding (tests/exactref.py) --
 every body under every setting must produce them, in a 'low' regime (nothing rounds: the statistics partials must add up
 to the exact totals) and a 'round' regime (>= 5 % of the outputs are exact bf16 ties), into outputs carved from a
-sentinel-filled buffer: both guards intact, no element left unwritten."""
+sentinel-filled buffer: both guards intact, no element left unwritten.
+
+The sets wrn, mlp and odd (k1_check.WRN_CASES / MLP_CASES / ODD_CASES) carry this to the small-channel layers: WideResNet-22's
+16 / 32 / 64-channel convs, strided 3x3 with TF SAME padding, strided 1x1 skips and stem; the MNIST MLP's dense layers and
+the 10-column heads, which ordinary dispatch sends to the direct kernels of conv_ref.hip; the explicit im2col and tiny-Cin
+paths.  There dX is wanted for every shape (the direct dgrad and the host fallbacks of ops.conv_dgrad / ops.conv_bwd), every
+wrapper form a shape does not take is asserted REFUSED with its outputs left all sentinel (verdict field "refused"), and the
+direct kernels run as forms of their own through force_ref=True (for `small` too); tests/test_exact_small_channel_cpu.py
+holds the conditions, mutants and workload shapes of these sets without a GPU."""
 import json
 import os
 import subprocess
@@ -49,7 +57,11 @@ SETS = [
     ('vgg', 10, 2, 1200),           # with and without the fused ReLU
     ('dw', 17, 1, 600),             # test_k3_k1_gpu.py's depthwise cases
     ('f32', 13, 1, 600),            # the fp32 twin, dense and masked
+    ('wrn', 10, 2, 600),            # WideResNet-22's layers: default / all-generic; dX and every wrapper form on every shape
+    ('mlp', 6, 1, 600),             # dense layers and heads on the direct kernels (no knob reaches them)
+    ('odd', 10, 2, 600),            # ragged shapes, cin / cout % 8 != 0: im2col, tiny Cin, the host fallbacks
 ]
+FULL = ('wrn', 'mlp', 'odd')        # the sets that assert the refusals of the forms a shape does not take
 
 
 @pytest.mark.skipif(not torch.cuda.is_available(), reason='needs a GPU')
@@ -57,12 +69,13 @@ SETS = [
 def test_exact_bits_and_guard_bands(name, cases, settings, timeout):
   out = _run(['--set', name], timeout)
   assert out['cases'] == cases and out['settings'] == settings
+  assert (out['refused'] > 0) == (name in FULL)
 
 
 @pytest.mark.skipif(not torch.cuda.is_available(), reason='needs a GPU')
 @pytest.mark.parametrize('name,cases,settings,timeout', SETS, ids=[s[0] for s in SETS])
 def test_exact_bits_on_an_exact_guarded_poisoned_workspace(name, cases, settings, timeout):
-  """The same nine walks with --workspace exact (tests/wsguard.py): every scratch request exactly as long as the size query
+  """The same walks with --workspace exact (tests/wsguard.py): every scratch request exactly as long as the size query
   said, between two 1 MiB guards, pre-filled with 0x00 and then 0xFF -- the expected bits do not depend on the summation
   order, so they hold whether a layer splits or not, and a query that under-reports, a kernel that reads scratch it did
   not initialise or a store outside the declared bytes all show.  Every set is walked in full, vgg included (both halves,

@@ -1,6 +1,8 @@
 """Parity of K3 (masked SGD-momentum, bit-exact vs the oracle), the weight
 shadow packer, and K1 (MFMA masked conv fwd/dgrad/wgrad vs an fp32 / fp64
-convolution of the same bf16-rounded operands)."""
+convolution of the same bf16-rounded operands).  The direct kernels (force_ref=True) are checked here within a tolerance;
+their bits, guard bands and ordinary dispatch are pinned by tests/k1_exact.py's sets wrn, mlp, odd and small
+(tests/test_k1_exact_gpu.py)."""
 import ctypes
 import os
 
