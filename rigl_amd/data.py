@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from rigl_amd import ops
+from rigl_amd.step_state import int32
 
 IMG_SIZE = 32
 
@@ -75,7 +76,7 @@ class DeviceCifar(object):
 
   def seek(self, step):
     """Sets the counter (an upload: outside any graph capture).  Replays pick the new value up: they read the counter."""
-    self.step.fill_(ops._i32(step))
+    self.step.fill_(int32(step))
 
   def last_indices(self):
     """Dataset indices of the batch produced last (needs ``with_indices=True``)."""

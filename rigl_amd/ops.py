@@ -12,6 +12,7 @@ import os
 import torch
 
 from rigl_amd import _lib
+from rigl_amd.step_state import int32 as _i32   # a Python int wrapped to int32 (TensorFlow's seeds, the step counters)
 from rigl_amd._lib import (ConvDesc, PackLayer, PruneRegrowLayer,
                            PruneRegrowParams, RiglError, check)
 
@@ -269,6 +270,11 @@ def _lr_device(lr, lr_device):
     _req(lr_device, torch.float32, 'lr_device')
     if lr_device.numel() != 1:
       raise ValueError('lr_device must hold 1 float')
+
+
+def lr_kwargs(lr):
+  """A rate held in one variable -- a host number or the fp32 [1] device tensor -- as the ``lr`` / ``lr_device`` argument."""
+  return {'lr_device': lr} if torch.is_tensor(lr) else {'lr': lr}
 
 
 def masked_sgd_momentum(w, grad, lr=None, momentum=None, mask_bits=None, mu=0.0,
@@ -1065,12 +1071,6 @@ def bn_bwd_reduce(x, dy, gamma, saved, relu, relu_bits, dgamma, dbeta):
 # ----------------------------------------------------------------------------
 # stateless random tensors (TensorFlow bit layout)
 # ----------------------------------------------------------------------------
-def _i32(v):
-  """A Python int wrapped to int32 (TensorFlow's seeds)."""
-  v = int(v) & 0xFFFFFFFF
-  return v - (1 << 32) if v >= 1 << 31 else v
-
-
 def stateless_random(n, seed0, seed1, dist, scale=1.0, shift=0.0, device=None,
                      out=None):
   """fp32 [n] = tf.random.stateless_{uniform|normal}([n], seed=[seed0, seed1])

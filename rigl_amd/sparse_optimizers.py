@@ -631,8 +631,8 @@ class SparseSnipOptimizer(PruningGetterMixin, train.Optimizer):
       ops.topk_mask_batched(items)
       self.graph.shadows_dirty = True
       self.is_snipped = True
-      if hasattr(self._optimizer, '_backward_done_for'):
-        self._optimizer._backward_done_for = None
+      if hasattr(self._optimizer, 'forget_backward'):
+        self._optimizer.forget_backward()
       return True
     self._optimizer.apply_gradients(grads_and_vars, global_step=global_step,
                                     name=name)

@@ -12,9 +12,8 @@ first update launch -- so a record holds the weights the gradients were taken at
 (``mask * (grad_scale * dense) + weight_decay * w``: the arena holds the DENSE gradient of masked kernels) and this step's
 rate.  Calls that apply nothing (RigL's mask-update iterations) leave no record; every global step gets exactly one.
 
-The device keeps its own step counter, which equals ``global_step.value`` in front of every call -- the protocol of the
-device learning-rate counter (train.GradientDescentOptimizer._device_lr_step): a host mirror, an upload when the two
-disagree, never during stream capture.  train.GraphedStep moves the mirror with its replays.
+The device keeps its own step counter, which equals ``global_step.value`` in front of every call: a step_state.StepCounter,
+kept by that module's protocol.  TrainingSummaries is one of its participants; its ``moved`` keeps the ring's ledger in step.
 
 Everything behind the copy of the ring is host arithmetic (``parse_slot`` / ``make_record`` / ``RingLedger``) and runs without
 a GPU.
@@ -24,19 +23,19 @@ import json
 import math
 
 import numpy as np
+import torch
 
 from rigl_amd import _lib
+from rigl_amd import ops
+from rigl_amd import train
+from rigl_amd import variables as V
+from rigl_amd.step_state import StepCounter, int32
 
 HEADER_BYTES = _lib.SUMMARY_HEADER_BYTES
 GROUP_BYTES = _lib.SUMMARY_GROUP_BYTES
 FLOAT_FIELDS = ('sumsq_g', 'sumsq_w', 'l1_w')
 COUNT_FIELDS = ('nz_w', 'mask_ones', 'nonfinite_g')
 _F32 = np.float32
-
-
-def _int32(v):
-  """v as the device's int32 counter holds it (two's-complement wrap-around)."""
-  return (int(v) + 2 ** 31) % 2 ** 32 - 2 ** 31
 
 
 def slot_bytes(n_entries):
@@ -133,14 +132,14 @@ class RingLedger:
     self._last = None                                 # (slot, the step it replaced or None): undo of the newest write
 
   def slot_of(self, step):
-    return _int32(step) % self.slots                  # python's % is non-negative: what the kernel computes
+    return int32(step) % self.slots                  # python's % is non-negative: what the kernel computes
 
   def wrote(self, step):
     slot = self.slot_of(step)
     before = self._live.pop(slot, None)
     if before is not None:
       self._dropped += 1
-    self._live[slot] = _int32(step)
+    self._live[slot] = int32(step)
     self._last = (slot, before)
 
   def undo(self):
@@ -183,28 +182,23 @@ class TrainingSummaries:
   MomentumOptimizer / AdamOptimizer or a sparse wrapper around one (its ``_optimizer``); ``ring``: slots of the device ring."""
 
   def __init__(self, graph, optimizer, ring=256, steps_per_epoch=None):
-    import torch  # pylint: disable=import-outside-toplevel
     self._graph = graph
     self._outer = optimizer
-    self._inner = getattr(optimizer, '_optimizer', optimizer)
-    if not hasattr(self._inner, '_summary_hook'):
+    self._inner = train.inner_optimizer(optimizer)
+    if not hasattr(self._inner, 'summary_hook'):
       raise TypeError('%s has no summary hook (expected a rigl_amd.train optimizer)' % type(self._inner).__name__)
     self._steps_per_epoch = steps_per_epoch
     self._ledger = RingLedger(ring)
     graph.finalize()
     if graph.W is None or not graph.W.is_cuda:
       raise _lib.RiglError(_lib.RIGL_EINVAL, 'training summaries need a graph on the GPU (no CPU path exists)')
-    self._step = torch.zeros(1, dtype=torch.int32, device=graph.W.device)
-    self.mirror = 0                                   # what the device counter holds
-    self._ring = None
+    self.counter = StepCounter(graph.W.device, "summaries'")
     self._build()
     graph.add_relayout_callback(self._build)
 
   # ---- the entry table ---------------------------------------------------------------------------------------------------
   def _build(self):
     """(Re)builds the layout and both tables from the graph's arenas; a relayout starts an empty ring."""
-    import torch  # pylint: disable=import-outside-toplevel
-    from rigl_amd import ops, variables as V  # pylint: disable=import-outside-toplevel
     g = self._graph
     masks = {l.weights.name: l.mask for l in g.layers if l.mask is not None}
     order = sorted(g.trainable_variables(), key=lambda v: v.offset)
@@ -230,47 +224,34 @@ class TrainingSummaries:
 
   # ---- the hook ----------------------------------------------------------------------------------------------------------
   def attach(self):
-    self._inner._summary_hook = self                  # pylint: disable=protected-access
+    self._inner.summary_hook = self
     return self
 
   def detach(self):
-    if self._inner._summary_hook is self:             # pylint: disable=protected-access
-      self._inner._summary_hook = None                # pylint: disable=protected-access
+    if self._inner.summary_hook is self:
+      self._inner.summary_hook = None
 
-  def advance_mirror(self, k):
-    """The device counter moved by ``k`` without a call of the hook: +1 a graph replay (which wrote a record), -1 undoing the
+  def fresh(self, global_step):
+    return self.counter.fresh(global_step)
+
+  def moved(self, k):
+    """The device counter moved by ``k``: +1 a launch of the hook or a graph replay (either wrote a record), -1 undoing the
     host side of a capture (which wrote none)."""
     if k == 1:
-      self._ledger.wrote(self.mirror)
+      self._ledger.wrote(self.counter.mirror)
     elif k == -1:
       self._ledger.undo()
     else:
-      raise ValueError('advance_mirror: k must be +1 or -1')
-    self.mirror = _int32(self.mirror + k)
+      raise ValueError('moved: k must be +1 or -1')
+    self.counter.moved(k)
 
-  def on_apply(self, inner, global_step, lr, grad_scale):
+  def on_apply(self, global_step, loss, lr, grad_scale):
     """Called by the inner optimizer's apply_gradients: behind the device learning-rate step, in front of the first update
-    launch.  ``lr`` None: the rate is the optimizer's device buffer."""
-    import torch  # pylint: disable=import-outside-toplevel
-    from rigl_amd import ops  # pylint: disable=import-outside-toplevel
-    if global_step is not None:
-      want = _int32(global_step.value)
-      if want != self.mirror:
-        if torch.cuda.is_current_stream_capturing():
-          raise RuntimeError('the summaries\' device step counter (%d) differs from global_step (%d) during graph capture: '
-                             'run one eager step after changing global_step' % (self.mirror, want))
-        self._step.fill_(want)
-        self.mirror = want
-    loss = inner._backward_done_for                   # pylint: disable=protected-access
-    acc = getattr(inner, '_accum', None)
-    if acc is not None and acc.covers(loss):
-      loss = acc.loss                                 # train.MicroBatches: the mean over the step's micro-batches, not the last one's
-    if not (torch.is_tensor(loss) and loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
-      loss = None
-    ops.summary_step(self._tables[bool(inner.dense_masked_update)], self._step, self._ring, self._ledger.slots,
-                     grad_scale=grad_scale, loss=loss.detach() if loss is not None else None, lr=lr,
-                     lr_device=inner._lr_dev if lr is None else None)   # pylint: disable=protected-access
-    self.advance_mirror(1)
+    launch.  ``loss``: the step's (GradientDescentOptimizer.step_loss); ``lr``: a float, or the device rate's tensor."""
+    self.counter.sync(global_step)
+    ops.summary_step(self._tables[bool(self._inner.dense_masked_update)], self.counter.tensor, self._ring, self._ledger.slots,
+                     grad_scale=grad_scale, loss=loss, **ops.lr_kwargs(lr))
+    self.moved(1)
 
   # ---- reading -----------------------------------------------------------------------------------------------------------
   def _drop_fraction(self):

@@ -19,7 +19,8 @@ applied inside the kernel rather than through the loss.
 ``learning_rate``: a float, a callable ``lr(global_step) -> float`` evaluated on the host every step (both reach the
 kernels by value), or a ``schedules.Schedule``.  On a GPU graph a Schedule takes the DEVICE path: the step counter and
 the rate live in device memory, one ``ops.lr_schedule_step`` per apply evaluates the schedule there, and the update
-kernels read the rate through a pointer -- so ``GraphedStep`` replays one graph through the whole schedule.
+kernels read the rate through a pointer -- so ``GraphedStep`` replays one graph through the whole schedule (the
+counter is kept by the protocol of ``step_state``).
 """
 import torch
 
@@ -27,6 +28,7 @@ from rigl_amd import _lib
 from rigl_amd import ops
 from rigl_amd import schedules
 from rigl_amd import variables as V
+from rigl_amd.step_state import StepCounter
 
 
 def get_or_create_global_step(graph=None):
@@ -39,9 +41,27 @@ def _lr_value(lr, global_step):
   return float(lr)
 
 
-def _int32(v):
-  """v as the device's int32 counter holds it (two's-complement wrap-around)."""
-  return (int(v) + 2 ** 31) % 2 ** 32 - 2 ** 31
+def inner_optimizer(optimizer):
+  """The optimizer of this module behind ``optimizer``: itself, or what a sparse wrapper holds as ``_optimizer``."""
+  return getattr(optimizer, '_optimizer', optimizer)
+
+
+def _gpu_scalar(t):
+  return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1
+
+
+class _DeviceLr:
+  """The device path of a schedules.Schedule: its step ``counter`` and the fp32 [1] ``rate`` the update kernels read.
+  ``step`` enqueues this step's rate: *rate = schedule(*counter); *counter += 1."""
+
+  def __init__(self, device):
+    self.counter = StepCounter(device, 'learning-rate')
+    self.rate = torch.zeros(1, dtype=torch.float32, device=device)
+
+  def step(self, schedule, global_step):
+    self.counter.sync(global_step)
+    ops.lr_schedule_step(schedule.descriptor(), self.counter.tensor, self.rate)
+    self.counter.moved(1)
 
 
 class Optimizer:
@@ -81,14 +101,13 @@ class GradientDescentOptimizer(Optimizer):
     self._grad_sync = grad_sync    # rigl_amd.dist.GradSync or None
     self._backward_done_for = None
     self.dense_masked_update = False   # DNW: apply the dense gradient to masked kernels too
-    # the device path of a schedules.Schedule: int32 [1] step counter, fp32 [1] rate, and what the counter holds (host mirror)
-    self._lr_step = None
-    self._lr_dev = None
-    self._lr_mirror = 0
+    # the _DeviceLr of a schedules.Schedule on a GPU graph.  Created by the first apply, an eager one (GraphedStep runs eager
+    # steps before it captures), so its buffers never belong to a graph-private pool
+    self.device_lr = None
     # summaries.TrainingSummaries.attach() sets it: called once per apply, in front of the first update launch.  None: no launch
-    self._summary_hook = None
+    self.summary_hook = None
     # the MicroBatches whose sum is pending or finished for the loss being minimised (set by its call), or None
-    self._accum = None
+    self.accumulation = None
 
   # ---- gradients -------------------------------------------------------------
   def compute_gradients(self, loss, var_list=None, **kwargs):
@@ -98,7 +117,7 @@ class GradientDescentOptimizer(Optimizer):
     del kwargs
     g = self.graph
     g.finalize()
-    acc = self._accum
+    acc = self.accumulation
     if acc is not None and loss is not None:
       acc.check_pending(loss)      # a sum pending for another loss: refused, never guessed
     if loss is not None and self._backward_done_for is not loss:
@@ -121,13 +140,25 @@ class GradientDescentOptimizer(Optimizer):
     of a GradSync, whose all-reduce leaves the sum over replicas, times the 1 / k of a MicroBatches accumulation finished for
     the loss that was backpropagated, which leaves the sum over micro-batches."""
     scale = self._grad_sync.grad_scale if self._grad_sync is not None else 1.0
-    acc = self._accum
+    acc = self.accumulation
     if acc is not None and acc.finished_for(self._backward_done_for):
       scale = scale * acc.inv_k
     return scale
 
+  def forget_backward(self):
+    """The last backward no longer counts: the next compute_gradients backpropagates its loss, whichever it is."""
+    self._backward_done_for = None
+
+  def step_loss(self):
+    """The loss of the step being applied, for its record: the micro-batch mean when a MicroBatches covers the loss that was
+    backpropagated, otherwise that loss; detached, or None where it is not one fp32 scalar on the GPU."""
+    loss, acc = self._backward_done_for, self.accumulation
+    if acc is not None and acc.finished_for(loss):
+      loss = acc.loss
+    return loss.detach() if _gpu_scalar(loss) else None
+
   def _ensure_slots(self):
-    self._ensure_lr_buffers()
+    """Creates the slot arenas (plain gradient descent has none)."""
 
   def lr_on_device(self):
     """True when the learning rate is a schedules.Schedule and the graph lives on a GPU: the rate is then computed and
@@ -135,35 +166,18 @@ class GradientDescentOptimizer(Optimizer):
     w = self.graph.W
     return isinstance(self._lr, schedules.Schedule) and w is not None and w.is_cuda
 
-  def _ensure_lr_buffers(self):
-    """The persistent step / rate buffers of the device path.  First reached in an eager step (GraphedStep runs eager steps
-    before it captures), so they never belong to a graph-private pool."""
-    if self._lr_step is None and self.lr_on_device():
-      dev = self.graph.W.device
-      self._lr_step = torch.zeros(1, dtype=torch.int32, device=dev)
-      self._lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
-      self._lr_mirror = 0
+  def lr_key(self, global_step):
+    """What a captured graph of this optimizer's step holds of the rate: the Schedule itself on the device path (the graph
+    evaluates it), otherwise the rate's value at ``global_step`` (a kernel argument, frozen at capture)."""
+    return self._lr if self.lr_on_device() else _lr_value(self._lr, global_step)
 
-  def _advance_lr_mirror(self, k):
-    """The device counter moved by ``k`` without this optimizer's doing (a graph replay: +1; undoing a capture's host side
-    effect: -1)."""
-    self._lr_mirror = _int32(self._lr_mirror + k)
-
-  def _device_lr_step(self, global_step):
-    """Enqueues this step's rate: *lr = schedule(*step); *step += 1.  Invariant: before it, the device counter equals
-    global_step.value (with global_step None it free-runs from 0).  Where the host mirror of the counter says otherwise --
-    after global_step.assign, a checkpoint restore, a wrapper that stepped it some other way -- the counter is uploaded
-    first; never during stream capture, where the upload would be replayed with its frozen value."""
-    if global_step is not None:
-      want = _int32(global_step.value)
-      if want != self._lr_mirror:
-        if torch.cuda.is_current_stream_capturing():
-          raise RuntimeError('the device step counter (%d) differs from global_step (%d) during graph capture: run one eager '
-                             'step after changing global_step' % (self._lr_mirror, want))
-        self._lr_step.fill_(want)
-        self._lr_mirror = want
-    ops.lr_schedule_step(self._lr.descriptor(), self._lr_step, self._lr_dev)
-    self._advance_lr_mirror(1)
+  def step_participants(self):
+    """The step_state participants of the next apply, each with ``fresh(global_step)`` and ``moved(k)``: the device rate's
+    counter on the device path (None until the first eager apply has allocated it) and the attached summaries."""
+    parts = [self.summary_hook] if self.summary_hook is not None else []
+    if self.lr_on_device():
+      parts.append(self.device_lr.counter if self.device_lr is not None else None)
+    return parts
 
   def apply_gradients(self, grads_and_vars, global_step=None, name=None):
     del name
@@ -190,14 +204,17 @@ class GradientDescentOptimizer(Optimizer):
                                   % (missing[:3], ' ...' if len(missing) > 3 else ''))
     self._ensure_slots()
     if self.lr_on_device():
-      self._device_lr_step(global_step)
-      lr = None                      # the update launches read self._lr_dev
+      if self.device_lr is None:
+        self.device_lr = _DeviceLr(g.W.device)
+      self.device_lr.step(self._lr, global_step)
+      lr = self.device_lr.rate       # the update launches read it on the device
     else:
       lr = _lr_value(self._lr, global_step)
     scale = self.update_scale()
     mu = float(self._momentum) if self._momentum is not None else 0.0
-    if self._summary_hook is not None:
-      self._summary_hook.on_apply(self, global_step, lr, scale)    # this step's record: the weights and gradients as they are now
+    if self.summary_hook is not None:
+      # this step's record: the weights and gradients as they are now
+      self.summary_hook.on_apply(global_step, self.step_loss(), lr, scale)
     # one launch per segment; weight decay is uniform inside a kernel segment
     for kind in (V.KIND_MASKED, V.KIND_DENSE):
       b, e = g.seg[kind]
@@ -218,9 +235,9 @@ class GradientDescentOptimizer(Optimizer):
       self._apply_range(b, e, None, lr, mu, 0.0, scale)
     self._finish()
     g.shadows_dirty = True
-    self._backward_done_for = None
-    if self._accum is not None:
-      self._accum.release()
+    self.forget_backward()
+    if self.accumulation is not None:
+      self.accumulation.release()
     if global_step is not None:
       global_step.value += 1
     return None
@@ -238,12 +255,11 @@ class GradientDescentOptimizer(Optimizer):
                         scale)
 
   def _apply_range(self, b, e, mask_bits, lr, mu, wd, scale):
-    """One update launch over arena elements [b, e) (K3).  ``lr`` None: the rate is read from the device buffer."""
+    """One update launch over arena elements [b, e) (K3).  ``lr``: a float, or the device rate's tensor."""
     g = self.graph
     ops.masked_sgd_momentum(
-        g.W[b:e], g.G[b:e], lr, lr_device=self._lr_dev if lr is None else None,
-        momentum=self._slot[b:e] if self._slot is not None else None,
-        mask_bits=mask_bits, mu=mu, weight_decay=wd, grad_scale=scale, nesterov=self._nesterov)
+        g.W[b:e], g.G[b:e], momentum=self._slot[b:e] if self._slot is not None else None,
+        mask_bits=mask_bits, mu=mu, weight_decay=wd, grad_scale=scale, nesterov=self._nesterov, **ops.lr_kwargs(lr))
 
   def _finish(self):
     """After the last segment of a step (tf.train.Optimizer._finish)."""
@@ -264,7 +280,6 @@ class MomentumOptimizer(GradientDescentOptimizer):
 
   def _ensure_slots(self):
     g = self.graph
-    self._ensure_lr_buffers()
     if self._slot is None or self._slot.numel() != g.W.numel():
       old = self._slot
       self._slot = torch.zeros_like(g.W)
@@ -305,7 +320,6 @@ class AdamOptimizer(GradientDescentOptimizer):
 
   def _ensure_slots(self):
     g = self.graph
-    self._ensure_lr_buffers()
     if self._slot is None or self._slot.numel() != g.W.numel():
       if self._slot is not None:
         raise RuntimeError('variables were added after the Adam slots were created')
@@ -331,9 +345,9 @@ class AdamOptimizer(GradientDescentOptimizer):
   def _apply_range(self, b, e, mask_bits, lr, mu, wd, scale):
     del mu
     g = self.graph
-    ops.masked_adam(g.W[b:e], g.G[b:e], self._slot[b:e], self._slot_v[b:e], self._beta_powers, lr,
-                    lr_device=self._lr_dev if lr is None else None, beta1=self._beta1, beta2=self._beta2,
-                    epsilon=self._epsilon, mask_bits=mask_bits, weight_decay=wd, grad_scale=scale)
+    ops.masked_adam(g.W[b:e], g.G[b:e], self._slot[b:e], self._slot_v[b:e], self._beta_powers, beta1=self._beta1,
+                    beta2=self._beta2, epsilon=self._epsilon, mask_bits=mask_bits, weight_decay=wd, grad_scale=scale,
+                    **ops.lr_kwargs(lr))
 
   def _finish(self):
     ops.adam_advance(self._beta_powers, self._beta1, self._beta2)
@@ -372,8 +386,8 @@ class MicroBatches:
     k = int(micro_batches)
     if k < 1 or k != micro_batches:
       raise ValueError('micro_batches must be an integer >= 1, got %r' % (micro_batches,))
-    inner = getattr(optimizer, '_optimizer', optimizer)
-    if not hasattr(inner, '_accum'):
+    inner = inner_optimizer(optimizer)
+    if not hasattr(inner, 'accumulation'):
       raise TypeError('%s cannot accumulate (expected a rigl_amd.train optimizer or a wrapper around one)' % type(inner).__name__)
     sync = getattr(inner, '_grad_sync', None)
     if sync is not None and getattr(sync, 'enabled', False):
@@ -412,7 +426,7 @@ class MicroBatches:
 
   @staticmethod
   def _check_loss(loss):
-    if not (torch.is_tensor(loss) and loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
+    if not _gpu_scalar(loss):
       raise TypeError('MicroBatches: loss_fn must return one fp32 scalar on the GPU')
     return loss.detach()
 
@@ -429,7 +443,7 @@ class MicroBatches:
     # stream they were created on -- for ever the stream of the first step.  A step captured on another stream would pull
     # that stream into its capture.  So the references taken here live from this call to the apply (or the next call).
     self._pending = self._done_for = None
-    inner._backward_done_for = None                     # pylint: disable=protected-access
+    inner.forget_backward()
     for i in range(self.micro_batches - 1):
       loss = self._loss_fn(*args, **kwargs)
       scalar = self._check_loss(loss)
@@ -441,7 +455,7 @@ class MicroBatches:
     loss = self._loss_fn(*args, **kwargs)
     self._check_loss(loss)
     self._pending = loss
-    inner._accum = self                                 # pylint: disable=protected-access
+    inner.accumulation = self
     return loss
 
   # ---- the inner optimizer's side ------------------------------------------------------------------------------------------
@@ -465,10 +479,6 @@ class MicroBatches:
     """The update was applied: the step's loss is let go of (see __call__)."""
     self._done_for = None
 
-  def covers(self, loss):
-    """True when ``loss`` has a pending or finished accumulation: its record's loss is ``self.loss``."""
-    return loss is not None and (self._pending is loss or self._done_for is loss)
-
 
 class GraphedStep:
   """One training step replayed from a captured HIP graph (torch.cuda.CUDAGraph over the kernels the
@@ -486,10 +496,9 @@ class GraphedStep:
   changes every step -- a warm-up, a cosine -- nothing is captured and the steps run eagerly).  A learning rate
   given as a ``schedules.Schedule`` is NOT frozen: the optimizer keeps the step counter and the rate in device
   memory and the captured step itself evaluates the schedule and advances the counter (ops.lr_schedule_step), so
-  ONE graph, keyed on the schedule object, is replayed through warm-up, drops and restarts alike.  A replay
-  moves the optimizer's host mirror of that counter together with the global step; when the two disagree
-  (``global_step.assign``, a checkpoint restore) the call runs eagerly, which uploads the counter -- a graph is
-  never replayed against a stale counter.  The loss tensor returned is the captured step's output buffer.
+  ONE graph, keyed on the schedule object, is replayed through warm-up, drops and restarts alike.  That counter
+  and whatever else the optimizer names (``step_participants``) is kept by the protocol of ``step_state``: a call that finds
+  one stale runs eagerly -- a graph is never replayed against a stale counter.  The loss tensor is the captured step's output.
 
   ``loss_fn`` must read its inputs from fixed device buffers (copy each new batch into them); a ``MicroBatches`` as ``loss_fn``
   puts its k forward / backward passes and the one update into the same graph.  Data-parallel
@@ -502,17 +511,14 @@ class GraphedStep:
     self._gs = global_step
     self._warmup = warmup
     self._graphs = {}          # lr value (or the Schedule object on the device path) -> (CUDAGraph, loss tensor)
-    inner = getattr(optimizer, '_optimizer', optimizer)
-    self._inner = inner
-    sync = getattr(inner, '_grad_sync', None)
+    self._inner = inner_optimizer(optimizer)
+    sync = getattr(self._inner, '_grad_sync', None)
     self._eager_only = (sync is not None and getattr(sync, 'enabled', False)) or not torch.cuda.is_available()
     self.replays = 0
     self.eager_steps = 0
     self._ws_gen = ops.WORKSPACE_GENERATION
-    self._last_key = None      # learning-rate key of the previous ordinary step and how many steps it has been stable
-    self._stable = 0
-    self._summ = getattr(inner, '_summary_hook', None)   # the summaries hook the cached graphs were captured with
-    self._stable_needed = 1    # capture at the second consecutive ordinary step with the same learning rate
+    self._last_key = None      # learning-rate key of the previous ordinary step: the second consecutive one at a rate captures
+    self._parts = None         # the step_state participants the cached graphs were captured with
 
   def _is_update(self):
     o = self._opt
@@ -529,82 +535,69 @@ class GraphedStep:
   def __call__(self):
     if self._eager_only or self._is_update():
       return self._eager()
-    inner = self._inner
-    dev_lr = inner.lr_on_device() if hasattr(inner, 'lr_on_device') else False
-    if dev_lr:
-      if inner._lr_step is None or _int32(self._gs.value) != inner._lr_mirror:   # pylint: disable=protected-access
-        return self._eager()                                       # allocates / uploads the device counter (never in a graph)
-      key = inner._lr                                              # pylint: disable=protected-access
-    else:
-      key = _lr_value(inner._lr, self._gs)                         # pylint: disable=protected-access
-    # attached training summaries keep a device step counter too, under the same protocol: a stale one is uploaded by an eager
-    # call, and graphs captured with another hook (or none) enqueue another set of launches
-    summ = getattr(inner, '_summary_hook', None)
-    if summ is not self._summ:
+    parts = self._inner.step_participants()
+    if parts != self._parts:       # graphs captured with other participants (another hook, or none) enqueue another set of launches
       self._graphs.clear()
-      self._summ = summ
-    if summ is not None and _int32(self._gs.value) != summ.mirror:
-      return self._eager()
+      self._parts = parts
+    if any(p is None or not p.fresh(self._gs) for p in parts):
+      return self._eager()         # allocates / uploads the stale device counter (never in a graph)
     if self._ws_gen != ops.WORKSPACE_GENERATION:
       # a scratch buffer was (re)allocated since the graphs were captured (an eager mask update outgrew one, typically):
       # EVERY cached graph may point at the old buffer -- drop them all and capture again.  Checked before every replay,
       # so no graph is ever replayed against a freed buffer (ops.workspace keeps nothing alive for them).
       self._graphs.clear()
       self._ws_gen = ops.WORKSPACE_GENERATION
-    ent = self._graphs.get(key)
-    if ent is None:
-      #  a learning rate that changes every step (linear warm-up, cosine) never reuses a graph keyed on its
-      # value: while the key keeps changing, run plain eager steps and do not capture; once it has been stable for
-      # `_stable_needed` consecutive steps (the constant plateaus of a piecewise schedule), capture again.
-      if not dev_lr:                                               # (the device path has one key for the whole schedule)
-        if key == self._last_key:
-          self._stable += 1
-        else:
-          self._stable = 0
-          self._last_key = key
-        if self._stable < self._stable_needed:
-          return self._eager()
-      if self._warmup > 0:                                         # allocator / workspace caches / descriptors settle first
-        self._warmup -= 1
+    key = self._inner.lr_key(self._gs)
+    if key in self._graphs:
+      self._last_key = key
+      return self._replay(key, parts)
+    #  a learning rate that changes every step (linear warm-up, cosine) never reuses a graph keyed on its
+    # value: while the key keeps changing, run plain eager steps and do not capture; at the second consecutive step with
+    # the same key (the constant plateaus of a piecewise schedule), capture again.
+    if not self._inner.lr_on_device():   # (the device path has one key for the whole schedule)
+      stable, self._last_key = key == self._last_key, key
+      if not stable:
         return self._eager()
-      side = torch.cuda.Stream()
-      side.wait_stream(torch.cuda.current_stream())
-      with torch.cuda.stream(side):
-        out = self._eager()                                        # THIS call's step, on a side stream as torch's capture recipe asks
-      torch.cuda.current_stream().wait_stream(side)
-      torch.cuda.synchronize()
-      if self._is_update() or (not dev_lr and _lr_value(inner._lr, self._gs) != key):   # pylint: disable=protected-access
-        return out                                                 # the next iteration is not an ordinary one at this lr: capture later
-      gen0 = ops.WORKSPACE_GENERATION
-      step1 = self._gs.value
-      graph = torch.cuda.CUDAGraph()
-      with torch.cuda.graph(graph):
-        loss = self._loss_fn()
-        self._opt.minimize(loss, self._gs)                         # capture enqueues nothing; undo its host side effect:
-      self._gs.value = step1
-      if dev_lr:
-        inner._advance_lr_mirror(-1)                               # pylint: disable=protected-access
-      if summ is not None:
-        summ.advance_mirror(-1)
-      if gen0 != ops.WORKSPACE_GENERATION or gen0 != self._ws_gen:
-        # a buffer grew during the pre-capture step or the capture itself: graphs cached under other learning rates are
-        # stale, and this one may hold both addresses -- keep none, the next call captures on settled buffers
-        self._graphs.clear()
-        self._ws_gen = ops.WORKSPACE_GENERATION
-        return out
-      if len(self._graphs) >= 16:
-        self._graphs.pop(next(iter(self._graphs)))                 # bound the cache (piecewise-constant schedules have few values)
-      self._graphs[key] = (graph, loss)
+    if self._warmup > 0:           # allocator / workspace caches / descriptors settle first
+      self._warmup -= 1
+      return self._eager()
+    return self._capture(key, parts)
+
+  def _capture(self, key, parts):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+      out = self._eager()          # THIS call's step, on a side stream as torch's capture recipe asks
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    if self._is_update() or self._inner.lr_key(self._gs) != key:
+      return out                   # the next iteration is not an ordinary one at this lr: capture later
+    gen0 = ops.WORKSPACE_GENERATION
+    step1 = self._gs.value
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+      loss = self._loss_fn()
+      self._opt.minimize(loss, self._gs)
+    self._gs.value = step1         # capture enqueues nothing; undo its host side effect
+    for p in parts:
+      p.moved(-1)
+    if gen0 != ops.WORKSPACE_GENERATION or gen0 != self._ws_gen:
+      # a buffer grew during the pre-capture step or the capture itself: graphs cached under other learning rates are
+      # stale, and this one may hold both addresses -- keep none, the next call captures on settled buffers
+      self._graphs.clear()
+      self._ws_gen = ops.WORKSPACE_GENERATION
       return out
-    graph, loss = ent
-    if not dev_lr:
-      self._last_key, self._stable = key, self._stable_needed
+    if len(self._graphs) >= 16:
+      self._graphs.pop(next(iter(self._graphs)))   # bound the cache (piecewise-constant schedules have few values)
+    self._graphs[key] = (graph, loss)
+    return out
+
+  def _replay(self, key, parts):
+    graph, loss = self._graphs[key]
     graph.replay()
     self._gs.value += 1
-    if dev_lr:
-      inner._advance_lr_mirror(1)                                  # pylint: disable=protected-access
-    if summ is not None:
-      summ.advance_mirror(1)                                       # the replay wrote this step's record
-    self._inner.graph.shadows_dirty = True                        # the replayed update rewrote the weights
+    for p in parts:
+      p.moved(1)                   # (the summaries: the replay wrote this step's record)
+    self._inner.graph.shadows_dirty = True   # the replayed update rewrote the weights
     self.replays += 1
     return loss

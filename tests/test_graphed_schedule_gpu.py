@@ -68,16 +68,16 @@ def _run(mode, sched, calls, optimizer='momentum', method='rigl', assign=None, w
     losses.append(float(run().detach().float()))
     if st is not None and st.replays > r0:
       replay_steps.append(s0)
-    if inner._lr_dev is not None:
-      rates.append((s0, int(gs.value), float(inner._lr_dev.cpu()[0])))
+    if inner.device_lr is not None:
+      rates.append((s0, int(gs.value), float(inner.device_lr.rate.cpu()[0])))
   torch.cuda.synchronize()
   out = dict(W=g.W.cpu().numpy().copy(), A=inner._slot.cpu().numpy().copy(), B=g.BITS.cpu().numpy().copy(),
              gs=int(gs.value), losses=losses, rates=rates, replay_steps=replay_steps)
   if optimizer == 'adam':
     out['V'] = inner._slot_v.cpu().numpy().copy()
-  if inner._lr_step is not None:
-    out['counter'] = int(inner._lr_step.cpu()[0])
-    out['mirror'] = inner._lr_mirror
+  if inner.device_lr is not None:
+    out['counter'] = int(inner.device_lr.counter.tensor.cpu()[0])
+    out['mirror'] = inner.device_lr.counter.mirror
   if st is not None:
     out.update(replays=st.replays, eager=st.eager_steps, n_graphs=len(st._graphs), keys=list(st._graphs))
   return out

@@ -169,10 +169,10 @@ def test_host_faces_and_the_alias():
 
 def test_optimizer_takes_the_host_path_without_a_gpu_graph():
   """A Schedule on a CPU graph (and host_only() anywhere) is an ordinary callable learning rate."""
-  from rigl_amd import train
+  from rigl_amd import step_state, train
   s = S.piecewise_constant([1], [0.5, 0.25])
 
   class GS:
     value = 2
   assert train._lr_value(s, GS) == 0.25 and train._lr_value(s.host_only(), GS) == 0.25
-  assert train._int32(2 ** 31) == -2 ** 31 and train._int32(-1) == -1
+  assert step_state.int32(2 ** 31) == -2 ** 31 and step_state.int32(-1) == -1

@@ -233,6 +233,6 @@ def test_ring_of_4_slots_and_11_steps_through_read():
     assert r['pruning/conv_a/mask/sparsity'] == S.mask_summaries(g.get_masks())['pruning/conv_a/mask/sparsity']
   # detached: the optimizer enqueues no summary launch and the ring stays as it is
   summ.detach()
-  assert opt._summary_hook is None
+  assert opt.summary_hook is None
   opt.apply_gradients(None, global_step=gs)
   assert summ.read() == ([], 0)

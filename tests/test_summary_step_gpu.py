@@ -69,7 +69,7 @@ def _run(mode, rate, attach=True, optimizer='momentum', method='rigl', calls=CAL
     losses.append(loss)
     if int(gs.value) == s0 + 1:
       applied.append((s0, loss))
-      used_rates[s0] = float(inner._lr_dev.cpu()[0]) if inner._lr_dev is not None else float(F32(inner._lr))
+      used_rates[s0] = float(inner.device_lr.rate.cpu()[0]) if inner.device_lr is not None else float(F32(inner._lr))
   torch.cuda.synchronize()
   out = dict(W=g.W.cpu().numpy().copy(), A=inner._slot.cpu().numpy().copy(), B=g.BITS.cpu().numpy().copy(), gs=int(gs.value),
              losses=losses, applied=applied, rates=used_rates, snaps=snaps)
@@ -80,7 +80,7 @@ def _run(mode, rate, attach=True, optimizer='momentum', method='rigl', calls=CAL
   if summ is not None:
     out['records'], out['dropped'] = summ.read(per_variable=True)
     out['layout'] = summ.layout
-    out['mirror'], out['counter'] = summ.mirror, int(summ._step.cpu()[0])
+    out['mirror'], out['counter'] = summ.counter.mirror, int(summ.counter.tensor.cpu()[0])
     out['variables'] = [(v.name, v.offset, v.numel, v.kind, v.weight_decay)
                         for v in sorted(g.trainable_variables(), key=lambda v: v.offset)]
     out['drop_fraction'] = {s: float(opt.get_drop_fraction(s, True)) for s, _ in applied} if method == 'rigl' else None

@@ -86,8 +86,8 @@ def bench_step(args):
               'global_step': int(runs[a]['gs'].value)}
     inner = runs[a]['inner']
     if inner.lr_on_device():
-      out[a]['device_counter'] = int(inner._lr_step.cpu()[0])                                   # pylint: disable=protected-access
-      out[a]['device_lr'] = float(inner._lr_dev.cpu()[0])                                       # pylint: disable=protected-access
+      out[a]['device_counter'] = int(inner.device_lr.counter.tensor.cpu()[0])
+      out[a]['device_lr'] = float(inner.device_lr.rate.cpu()[0])
   med = lambda a: out[a]['images_per_s_median']
   out['warmup_dev_over_const'] = round(med('warmup_dev') / med('const'), 4)
   out['sgdr_dev_over_const'] = round(med('sgdr_dev') / med('const'), 4)
