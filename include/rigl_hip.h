@@ -518,6 +518,64 @@ int rigl_grad_accumulate(int64_t n, float* acc, float* grad, int32_t mode,
                          float* loss_mean /* device [1], written in LAST only */,
                          float inv_k, int32_t max_blocks, rigl_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Training-state snapshots: a table of device regions <-> ONE packed device
+ * image, at copy rate, with a digest per region.
+ *   Replaces: the per-variable save / restore ops of tf.train.Saver, which
+ *   the reference's Estimator drivers run every save_checkpoints_steps
+ *   (rigl/imagenet_resnet/imagenet_train_eval.py:740-741, rigl/cifar_resnet/
+ *   resnet_train_eval.py:517-519) -- one copy per tensor -- with one gather pass into a
+ *   staging buffer, after which the training stream is free again.
+ * LAYOUT: region r starts in `packed` at the running sum of the earlier
+ * regions' byte counts, each rounded up to RIGL_STATE_ALIGN (256).  gather
+ * writes the padding behind a region as zero bytes (the image depends on the
+ * state alone); scatter never reads the padding and writes nothing outside
+ * [ptr, ptr + bytes) of any region.  Copies are bit for bit: NaN payloads,
+ * signed zeros and subnormals are kept.
+ * DIGEST: per region, over its uint32 words w_0 .. w_{m-1} (m = bytes / 4,
+ * padding excluded):  s1 = sum w_i mod 2^64,  s2 = sum (i + 1) * w_i mod 2^64,
+ * written as digests[2r], digests[2r + 1].  gather digests the words it read,
+ * scatter the words it wrote.  Integer arithmetic only: the bits depend on the
+ * data alone, not on the grid, on max_blocks (the grid cap, 0 = default) or on
+ * the order of the partial sums.  Every call writes every digest and reads
+ * nothing the buffer held before; a zero-length region has digest (0, 0).
+ * The digest is an integrity check against truncation, misplacement and bit
+ * rot.  It is NOT cryptographic: forging a collision is easy.
+ * A region is cut into chunks of RIGL_STATE_CHUNK words, one workgroup per
+ * chunk at a time (a long region is spread over the whole grid); the chunk
+ * partials live in the workspace and one finalize launch sums them.  16-byte
+ * accesses on both sides where the region pointer is 16-byte aligned (every
+ * torch allocation and arena slice is; the rates on record were measured on
+ * such regions only).  A region pointer that is only 4-byte aligned keeps
+ * them on the packed side and takes four 4-byte accesses per lane on its own
+ * side: correct and tested, its rate not measured.
+ * Capture-safe: `regions` is a HOST array, consumed before the call returns
+ * and passed to the kernels by value, RIGL_STATE_BATCH regions per launch.
+ * Launches: ceil(n / 64) + 1; none for n == 0.
+ * Refused with nothing launched and nothing written: RIGL_EINVAL for a region
+ * pointer that is not 4-byte aligned, bytes negative or no multiple of 4, a
+ * NULL pointer with bytes > 0, packed not 256-byte aligned, digests not
+ * 8-byte aligned, n < 0, max_blocks < 0; RIGL_EWORKSPACE for a workspace that
+ * is NULL or shorter than rigl_state_workspace_bytes(regions, n).
+ * ---------------------------------------------------------------------- */
+#define RIGL_STATE_ALIGN 256
+#define RIGL_STATE_CHUNK 16384
+#define RIGL_STATE_BATCH 64
+typedef struct RiglStateRegion {
+  void* ptr;       /* device memory, 4-byte aligned */
+  int64_t bytes;   /* a multiple of 4 */
+} RiglStateRegion;
+size_t rigl_state_packed_bytes(const RiglStateRegion* regions /* host */, int32_t n);
+size_t rigl_state_workspace_bytes(const RiglStateRegion* regions /* host */, int32_t n);
+int rigl_state_gather(const RiglStateRegion* regions /* host */, int32_t n, void* packed,
+                      uint64_t* digests /* device [2n] */, void* workspace,
+                      size_t workspace_size /* bytes */, int32_t max_blocks,
+                      rigl_stream_t stream);
+int rigl_state_scatter(const RiglStateRegion* regions /* host */, int32_t n,
+                       const void* packed, uint64_t* digests /* device [2n] */,
+                       void* workspace, size_t workspace_size /* bytes */,
+                       int32_t max_blocks, rigl_stream_t stream);
+
 /* bf16 shadows of mask*W for the conv kernels:  hwio[i] = bf16(mask_i?w_i:0)
  * in flat HWIO order (dgrad operand) and ohwi = the [cout][kh*kw*cin]
  * transpose (fwd operand).  Either output may be NULL.  k = kh*kw*cin.      */

@@ -119,6 +119,16 @@ class SummaryEntry(C.Structure):
               ('weight_decay', C.c_float), ('apply_mask', C.c_int32)]
 
 
+STATE_ALIGN = 256             # RIGL_STATE_ALIGN: bytes, a region's offset in the packed image
+STATE_CHUNK = 16384           # RIGL_STATE_CHUNK: words one workgroup moves at a time
+STATE_BATCH = 64              # RIGL_STATE_BATCH: regions per copy launch
+
+
+class StateRegion(C.Structure):
+  """RiglStateRegion: one device region of rigl_state_gather / rigl_state_scatter."""
+  _fields_ = [('ptr', C.c_void_p), ('bytes', C.c_int64)]
+
+
 class ProfLaunch(C.Structure):
   """RiglProfLaunch: one timed K1 / K2 / K3 dispatch."""
   _fields_ = [('kind', C.c_int32), ('tag', C.c_int32 * 6), ('ms', C.c_float)]
@@ -157,6 +167,10 @@ SIGNATURES = {
     'rigl_summary_workspace_bytes': (_SZ, [C.POINTER(SummaryEntry), _I32]),
     'rigl_summary_step': (C.c_int, [C.POINTER(SummaryEntry), _I32, _F, _P, _P, _F, _P, _P, _I32, _P, _SZ, _I32, _P]),
     'rigl_grad_accumulate': (C.c_int, [_I64, _P, _P, _I32, _P, _P, _P, _F, _I32, _P]),
+    'rigl_state_packed_bytes': (_SZ, [C.POINTER(StateRegion), _I32]),
+    'rigl_state_workspace_bytes': (_SZ, [C.POINTER(StateRegion), _I32]),
+    'rigl_state_gather': (C.c_int, [C.POINTER(StateRegion), _I32, _P, _P, _P, _SZ, _I32, _P]),
+    'rigl_state_scatter': (C.c_int, [C.POINTER(StateRegion), _I32, _P, _P, _P, _SZ, _I32, _P]),
     'rigl_pack_weights': (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
     'rigl_pack_weights_batched': (C.c_int, [C.POINTER(PackLayer), _I32, _P]),
     'rigl_conv2d_workspace_bytes': (_SZ, [C.POINTER(ConvDesc), _I32]),

@@ -423,6 +423,63 @@ def grad_accumulate(acc, grad, mode, loss=None, loss_acc=None, loss_mean=None, i
                                          _ptr(loss_mean), float(inv_k), int(max_blocks), _stream()))
 
 
+def state_table(tensors):
+  """The host table of rigl_state_gather / rigl_state_scatter: one region per tensor (contiguous, on one GPU, a whole number
+  of 4-byte words).  The table holds raw pointers: the caller keeps the tensors alive."""
+  arr = (_lib.StateRegion * max(len(tensors), 1))()
+  for i, t in enumerate(tensors):
+    if not t.is_cuda:
+      raise RiglError(_lib.RIGL_EINVAL, 'state_table: region %d must live on the GPU (no CPU path exists)' % i)
+    if not t.is_contiguous():
+      raise ValueError('state_table: region %d must be contiguous' % i)
+    nbytes = t.numel() * t.element_size()
+    if nbytes % 4:
+      raise ValueError('state_table: region %d has %d bytes, no multiple of 4' % (i, nbytes))
+    arr[i].ptr = t.data_ptr() if nbytes else None
+    arr[i].bytes = nbytes
+  return arr, len(tensors)
+
+
+def state_packed_bytes(table):
+  arr, n = table
+  return int(_lib.load().rigl_state_packed_bytes(arr, n))
+
+
+def state_workspace_bytes(table):
+  arr, n = table
+  return int(_lib.load().rigl_state_workspace_bytes(arr, n))
+
+
+def _state_move(fn, table, packed, digests, max_blocks, ws):
+  arr, n = table
+  _req(packed, torch.uint8, 'packed')
+  _req(digests, torch.int64, 'digests')
+  lib = _lib.load()
+  if packed.numel() < lib.rigl_state_packed_bytes(arr, n):
+    raise ValueError('packed holds %d bytes, the table needs %d' % (packed.numel(), lib.rigl_state_packed_bytes(arr, n)))
+  if digests.numel() < 2 * n:
+    raise ValueError('digests holds %d words, the table needs %d' % (digests.numel(), 2 * n))
+  need = lib.rigl_state_workspace_bytes(arr, n)
+  if ws is None:
+    ws = workspace(need, packed.device, 'state')
+  else:
+    _req(ws, torch.uint8, 'workspace')
+  check(getattr(lib, fn)(arr, n, _ptr(packed), _ptr(digests), _ptr(ws), ws.numel(), int(max_blocks), _stream()))
+
+
+def state_gather(table, packed, digests, max_blocks=0, workspace_buffer=None):
+  """The regions of ``table`` (state_table) into ``packed`` (uint8, 256-byte aligned, state_packed_bytes): region r at the
+  running sum of the earlier sizes, each rounded up to 256, zero bytes in between; ``digests`` (int64 [2n], the uint64 sums'
+  bits) gets (s1, s2) of every region from the words read (rigl_state_gather).  Kernels only; the scratch is ``workspace_buffer`` (uint8, state_workspace_bytes) or ops.workspace."""
+  _state_move('rigl_state_gather', table, packed, digests, max_blocks, workspace_buffer)
+
+
+def state_scatter(table, packed, digests, max_blocks=0, workspace_buffer=None):
+  """``packed`` back into the regions of ``table``, in place; ``digests`` gets (s1, s2) of every region from the words written
+  (rigl_state_scatter).  The padding of ``packed`` is not read and nothing outside a region is written."""
+  _state_move('rigl_state_scatter', table, packed, digests, max_blocks, workspace_buffer)
+
+
 def pack_weights_batched(layers):
   """layers: list of (w fp32 [k*cout], mask_bits|None, k, cout, hwio|None,
   ohwi|None)."""
