@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 2   # include/rigl_hip.h RIGL_ABI_VERSION this mirror was written against
+ABI_VERSION = 3   # include/rigl_hip.h RIGL_ABI_VERSION this mirror was written against
 LIB_PATH = os.environ.get('RIGL_HIP_LIB') or os.path.join(_HERE, 'lib', 'librigl_hip.so')   # override: development builds
 
 RIGL_OK = 0
@@ -67,12 +67,6 @@ class ConvDesc(C.Structure):
               ('cout', C.c_int32), ('kh', C.c_int32), ('kw', C.c_int32),
               ('stride_h', C.c_int32), ('stride_w', C.c_int32),
               ('pad_top', C.c_int32), ('pad_left', C.c_int32)]
-
-
-class BnReduceFuse(C.Structure):
-  """RiglBnReduceFuse: the batch norm whose backward reductions ride in a dgrad epilogue."""
-  _fields_ = [('x', C.c_void_p), ('relu_bits', C.c_void_p), ('params', C.c_void_p), ('relu', C.c_int32),
-              ('partial', C.c_void_p), ('partial_floats', C.c_size_t)]
 
 
 class RandomItem(C.Structure):
@@ -185,9 +179,6 @@ SIGNATURES = {
     'rigl_masked_conv2d_fwd_bnrelu': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P]),
     'rigl_masked_conv2d_dgrad_acc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P,
                                                _P, _P, _SZ, _P]),
-    'rigl_conv2d_dgrad_stats_parts': (_I32, [C.POINTER(ConvDesc)]),
-    'rigl_masked_conv2d_bwd_bn': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _SZ,
-                                            C.POINTER(BnReduceFuse), _P]),
     'rigl_masked_conv2d_bwd': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     'rigl_masked_conv2d_bwd_masked': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     'rigl_conv2d_bwd_takes_masked_addend': (_I32, [C.POINTER(ConvDesc)]),
@@ -214,7 +205,6 @@ SIGNATURES = {
     'rigl_bn_fwd': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _F, _F, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     'rigl_bn_fwd_stats': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _F, _F, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _SZ, _P]),
     'rigl_bn_bwd': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
-    'rigl_bn_bwd_stats': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P]),
     'rigl_bn_bwd_reduce': (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     'rigl_crc32c': (C.c_uint32, [_P, _SZ, C.c_uint32]),
     'rigl_stateless_random': (C.c_int, [_P, _I64, _I32, _I32, _I32, _F, _F, _P]),

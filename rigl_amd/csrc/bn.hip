@@ -313,7 +313,7 @@ __global__ __launch_bounds__(THREADS) void k_fwd_apply(Geom G, const uint16_t* _
 }
 
 // Backward finalize: dgamma, dbeta and the per-channel coefficients of dx.  CL = 16 for the <= 512 partials of
-// k_reduce, 4 for the per-row-tile partials a dgrad epilogue leaves (rigl_masked_conv2d_bwd_bn: up to M / 128 of them).
+// k_reduce, 4 for more of them (the stem tail's, a raised "bn_max_parts").
 template <int CL>
 __global__ __launch_bounds__(THREADS) void k_bwd_finalize(Geom G, const float* __restrict__ partial,
                                                            const float* __restrict__ gamma, const float* __restrict__ invstd,
@@ -833,13 +833,13 @@ int rigl_bn_add_bn_bwd(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16
   return RIGL_OK;
 }
 
-// rigl_bn_bwd_stats, or (coef_out given: rigl_bn_bwd_reduce) its reduce + finalize alone with the coefficients left in the
+// rigl_bn_bwd, or (coef_out given: rigl_bn_bwd_reduce) its reduce + finalize alone with the coefficients left in the
 // caller's tensor instead of the workspace -- the same two launches on the same geometry either way.
 static int bn_bwd_impl(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16* y, const uint8_t* relu_bits,
                        const rigl_bf16* dy, const float* gamma,
                        const float* save_mean, const float* save_invstd, const float* save_scale, const float* save_shift,
                        int32_t relu, rigl_bf16* dx, rigl_bf16* dresidual, float* dgamma, float* dbeta,
-                       const float* stats, int32_t stats_parts, float* coef_out, void* workspace,
+                       float* coef_out, void* workspace,
                        size_t workspace_bytes, rigl_stream_t stream) {
   using namespace rigl;
   using namespace rigl::kbn;
@@ -849,7 +849,6 @@ static int bn_bwd_impl(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16
   if (relu && !y && !relu_bits && (!save_scale || !save_shift))
     return fail(RIGL_EINVAL, "rigl_bn_bwd: relu needs y, relu_bits or scale/shift");
   if (7 * (size_t)c * 4 > 65536) return fail(RIGL_EUNSUPPORTED, "rigl_bn_bwd: too many channels for the LDS parameter cache");
-  if (stats && stats_parts <= 0) return fail(RIGL_EINVAL, "rigl_bn_bwd_stats: stats_parts must be positive");
   const size_t need = rigl_bn_workspace_bytes(m, c);
   if (!workspace || workspace_bytes < need) return fail(RIGL_EWORKSPACE, "rigl_bn_bwd: workspace %zu < %zu", workspace_bytes, need);
   hipStream_t st = as_stream(stream);
@@ -858,25 +857,17 @@ static int bn_bwd_impl(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16
   float* coef = coef_out ? coef_out : reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)g.parts * 2 * c * 4, 256));
   dim3 rgrid((unsigned)g.parts, (unsigned)((g.cg + g.tpr - 1) / g.tpr));
   const int msk = relu_bits ? 2 : (y ? 1 : 0);
-  const float* red = partial;
-  if (stats) {
-    // the producer of dy (a dgrad epilogue, rigl_masked_conv2d_bwd_bn) left sum dz / sum dz * xhat per row tile:
-    // the reduction pass over dy and x is not run at all
-    red = stats;
-    g.parts = stats_parts;
-  } else {
 #define RIGL_BWD_REDUCE(R, K) hipLaunchKernelGGL((k_reduce<1, R, K>), rgrid, dim3(THREADS), 0, st, g, x, y, relu_bits, dy, save_mean, save_invstd, save_scale, save_shift, partial)
-    if (!relu) RIGL_BWD_REDUCE(false, 0);
-    else if (msk == 2) RIGL_BWD_REDUCE(true, 2);
-    else if (msk == 1) RIGL_BWD_REDUCE(true, 1);
-    else RIGL_BWD_REDUCE(true, 0);
+  if (!relu) RIGL_BWD_REDUCE(false, 0);
+  else if (msk == 2) RIGL_BWD_REDUCE(true, 2);
+  else if (msk == 1) RIGL_BWD_REDUCE(true, 1);
+  else RIGL_BWD_REDUCE(true, 0);
 #undef RIGL_BWD_REDUCE
-  }
-  if (g.parts > MAX_PARTS)      // (more partial rows than 512: a dgrad epilogue's, or a raised "bn_max_parts"; <16> is 0.7 us faster below it)
-    hipLaunchKernelGGL(k_bwd_finalize<4>, dim3((unsigned)((c + 3) / 4)), dim3(THREADS), 0, st, g, red, gamma,
+  if (g.parts > MAX_PARTS)      // (more partial rows than 512: a raised "bn_max_parts"; <16> is 0.7 us faster below it)
+    hipLaunchKernelGGL(k_bwd_finalize<4>, dim3((unsigned)((c + 3) / 4)), dim3(THREADS), 0, st, g, partial, gamma,
                        save_invstd, dgamma, dbeta, coef);
   else
-    hipLaunchKernelGGL(k_bwd_finalize<16>, dim3((unsigned)((c + 15) / 16)), dim3(THREADS), 0, st, g, red, gamma,
+    hipLaunchKernelGGL(k_bwd_finalize<16>, dim3((unsigned)((c + 15) / 16)), dim3(THREADS), 0, st, g, partial, gamma,
                        save_invstd, dgamma, dbeta, coef);
   if (coef_out) {                 // (the apply pass belongs to the consumer of dx: rigl_masked_conv2d_bwd_bnapply)
     RIGL_CHECK_LAUNCH("rigl_bn_bwd_reduce");
@@ -895,16 +886,6 @@ static int bn_bwd_impl(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16
   return RIGL_OK;
 }
 
-int rigl_bn_bwd_stats(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16* y, const uint8_t* relu_bits,
-                      const rigl_bf16* dy, const float* gamma,
-                      const float* save_mean, const float* save_invstd, const float* save_scale, const float* save_shift,
-                      int32_t relu, rigl_bf16* dx, rigl_bf16* dresidual, float* dgamma, float* dbeta,
-                      const float* stats, int32_t stats_parts, void* workspace,
-                      size_t workspace_bytes, rigl_stream_t stream) {
-  return bn_bwd_impl(m, c, x, y, relu_bits, dy, gamma, save_mean, save_invstd, save_scale, save_shift, relu, dx, dresidual, dgamma,
-                     dbeta, stats, stats_parts, nullptr, workspace, workspace_bytes, stream);
-}
-
 // rigl_bn_bwd without its apply launch: reduce + finalize, leaving dgamma, dbeta and coef[3][C] (a = gamma * invstd, b = mean dz,
 // c = mean dz * xhat) for a consumer that applies dx = a * (dz - b - xhat * c) itself (rigl_masked_conv2d_bwd_bnapply).
 int rigl_bn_bwd_reduce(int64_t m, int32_t c, const rigl_bf16* x, const uint8_t* relu_bits, const rigl_bf16* dy, const float* gamma,
@@ -913,7 +894,7 @@ int rigl_bn_bwd_reduce(int64_t m, int32_t c, const rigl_bf16* x, const uint8_t* 
   if (!coef) return rigl::fail(RIGL_EINVAL, "rigl_bn_bwd_reduce: coef is required");
   if (relu && !relu_bits) return rigl::fail(RIGL_EINVAL, "rigl_bn_bwd_reduce: relu needs relu_bits");
   return bn_bwd_impl(m, c, x, nullptr, relu ? relu_bits : nullptr, dy, gamma, save_mean, save_invstd, nullptr, nullptr, relu, nullptr,
-                     nullptr, dgamma, dbeta, nullptr, 0, coef, workspace, workspace_bytes, stream);
+                     nullptr, dgamma, dbeta, coef, workspace, workspace_bytes, stream);
 }
 
 int rigl_bn_bwd(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16* y, const uint8_t* relu_bits,
@@ -921,8 +902,8 @@ int rigl_bn_bwd(int64_t m, int32_t c, const rigl_bf16* x, const rigl_bf16* y, co
                 const float* save_mean, const float* save_invstd, const float* save_scale, const float* save_shift,
                 int32_t relu, rigl_bf16* dx, rigl_bf16* dresidual, float* dgamma, float* dbeta, void* workspace,
                 size_t workspace_bytes, rigl_stream_t stream) {
-  return rigl_bn_bwd_stats(m, c, x, y, relu_bits, dy, gamma, save_mean, save_invstd, save_scale, save_shift, relu, dx,
-                           dresidual, dgamma, dbeta, nullptr, 0, workspace, workspace_bytes, stream);
+  return bn_bwd_impl(m, c, x, y, relu_bits, dy, gamma, save_mean, save_invstd, save_scale, save_shift, relu, dx, dresidual, dgamma,
+                     dbeta, nullptr, workspace, workspace_bytes, stream);
 }
 
 // Eval entry points: the apply passes of the training forward with given scale / shift and no ReLU bits.

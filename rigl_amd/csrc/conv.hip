@@ -178,12 +178,7 @@ struct IgemmArgs {
   // wi % add_sw == 0, laid out [image][add_ho][add_wo][N]; every other pixel adds nothing.  (The gradient of a strided
   // 1x1 conv that read the same tensor: rigl_masked_conv2d_bwd_sub.)
   int add_sh, add_sw, add_ho, add_wo;
-  float* STATS;        // optional per-row-tile column statistics [tiles_m][2][N]: sum y, sum y^2 of the bf16 outputs (fwd);
-                       // with BNX (dgrad): sum dz, sum dz * xhat -- the batch-norm backward reductions of the produced tensor
-  const uint16_t* BNX; // dgrad only, optional: input x of the batch norm whose OUTPUT gradient this kernel produces ([M][N] like C)
-  const uint8_t* BNBITS;  // its 1-bit-per-element ReLU mask (relu(bn + residual)), or NULL: mask recomputed from BNX
-  const float* BNP;    // its saved statistics [4][N]: mean, invstd, scale, shift
-  int bn_relu;
+  float* STATS;        // optional per-row-tile column statistics [tiles_m][2][N]: sum y, sum y^2 of the bf16 outputs (fwd)
   int M, N, Cred;      // GEMM rows, columns, reduction channels per tap
   int KH, KW;
   int RH, RW;          // spatial size of the row space (ho,wo | h,w)
@@ -233,9 +228,6 @@ constexpr int igemm_smem_bytes() {
   constexpr int EPI_TAB = EPI + (CLS ? BM * 4 : 0);
   constexpr int EPI_ALL = EPI_TAB + ((MODE == 0 && !OUT_F32) ? NT * 8 : 0);
   constexpr int BASE = (NST * STAGE > EPI_ALL) ? NST * STAGE : EPI_ALL;
-  // dgrad: + the batch-norm statistics of the tile's columns, outside the ring where the 64 KB of static LDS allow it
-  constexpr int EPI_PRM = EPI_TAB + 4 * BN * 4;
-  if (MODE == 1 && !OUT_F32) return (BASE + 4 * BN * 4 <= 65536 && WM == 2) ? BASE + 4 * BN * 4 : (BASE > EPI_PRM ? BASE : EPI_PRM);
   return BASE;
 }
 
@@ -256,11 +248,7 @@ __device__ __forceinline__ void igemm_body(const IgemmArgs& P, unsigned char* sm
   constexpr int EPI_TAB = EPI + (CLS ? BM * 4 : 0);       // + per-row output pixel table
   constexpr int EPI_ALL = EPI_TAB + ((MODE == 0 && !OUT_F32) ? THREADS * 8 : 0);   // + column-statistics scratch
   constexpr int BASE = (NST * STAGE > EPI_ALL) ? NST * STAGE : EPI_ALL;
-  // dgrad: [4][BN] floats of batch-norm statistics -- behind ring and epilogue (filled at the top of the kernel) where
-  // the 64 KB static limit allows, else inside the epilogue area (filled in the epilogue)
-  constexpr bool PRM_OUT = MODE == 1 && !OUT_F32 && WM == 2 && BASE + 4 * BN * 4 <= 65536;
-  constexpr int PRM_OFF = PRM_OUT ? BASE : EPI_TAB;
-  constexpr int SMEM = (MODE == 1 && !OUT_F32) ? (PRM_OUT ? BASE + 4 * BN * 4 : (BASE > EPI_TAB + 4 * BN * 4 ? BASE : EPI_TAB + 4 * BN * 4)) : BASE;
+  constexpr int SMEM = BASE;
   static_assert(SMEM <= 65536 || WM == 4, "static LDS limit (the 512-thread variant uses dynamic LDS)");
   static_assert(STAGES == 2 || (BM % RPP == 0 && BN % RPP == 0), "LDS-DMA needs whole 1-KB wave rows");
   static_assert(SMEM == igemm_smem_bytes<TM, TN, BK, MODE, OUT_F32, CLS, STAGES, WM>(), "LDS size formula out of sync");
@@ -346,31 +334,6 @@ __device__ __forceinline__ void igemm_body(const IgemmArgs& P, unsigned char* sm
   __amdgpu_buffer_rsrc_t rsrcA = make_rsrc(P.A, P.a_bytes), rsrcB = make_rsrc(P.B, P.b_bytes);
   const u32x4 rsrcA4 = make_rsrc4(P.A, P.a_bytes), rsrcB4 = make_rsrc4(P.B, P.b_bytes);
   (void)rsrcA4; (void)rsrcB4;
-  // dgrad with batch-norm reductions in the epilogue: request the x tile (and its ReLU bits) NOW -- nothing depends on
-  // it until the tile is stored, so it travels under the whole K loop instead of stalling the epilogue.  (Class-major
-  // rows only know their pixels in the epilogue; those few strided layers load there.)
-  constexpr int E_CH = BN / 8, E_ITERS = OUT_F32 ? 1 : BM * E_CH / THREADS;
-  uint4 bnx[E_ITERS];
-  uint32_t bnb[E_ITERS];
-  const bool bnst = MODE == 1 && !OUT_F32 && P.BNX != nullptr;
-  if (PRM_OUT && bnst) {
-    // ... and the per-channel statistics of the tile's columns, into LDS of their own (not part of the ring)
-    float* bprm_w = reinterpret_cast<float*>(smem + PRM_OFF);
-    for (int i = tid; i < 4 * BN; i += THREADS) {
-      const int k = i / BN, c = i % BN;
-      bprm_w[i] = (n0 + c < P.N) ? P.BNP[k * P.N + n0 + c] : 0.f;
-    }
-  }
-  if (MODE == 1 && !OUT_F32 && !CLS && bnst) {
-#pragma unroll
-    for (int it = 0; it < E_ITERS; ++it) {
-      const int idx = it * THREADS + tid, row = idx / E_CH, ch = idx % E_CH;
-      const int m = m0 + row, n = n0 + ch * 8;
-      const bool ok = m < P.M && n < P.N;
-      bnx[it] = ok ? *reinterpret_cast<const uint4*>(P.BNX + (int64_t)m * P.ldc + n) : make_uint4(0u, 0u, 0u, 0u);
-      bnb[it] = (ok && P.BNBITS) ? (uint32_t)P.BNBITS[((int64_t)m * P.ldc + n) >> 3] : 0u;
-    }
-  }
 
   // (macros, not lambdas: by-reference lambda captures of the staging arrays
   //  kept them in scratch memory instead of registers)
@@ -653,124 +616,34 @@ __device__ __forceinline__ void igemm_body(const IgemmArgs& P, unsigned char* sm
     constexpr int CH = BN / 8, ITERS = BM * CH / THREADS;
     static_assert(BM * CH % THREADS == 0, "whole output chunks per thread");
     static_assert(THREADS % CH == 0, "a thread keeps its column chunk over all of its rows");
-    static_assert(CH == E_CH && ITERS == E_ITERS, "prefetch geometry == epilogue geometry");
-    float q0[8], q1[8];
-    if (!bnst) {
-      // fully unrolled, addend loads first: all of a thread's chunks are in flight together
-      // instead of one load -> add -> store round trip per chunk
-      uint4 addv[ITERS];
-      if (P.ADD) {
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-          const int idx = it * THREADS + tid, row = idx / CH, ch = idx % CH;
-          const int m = CLS ? rowpix[row] : m0 + row, n = n0 + ch * 8;
-          bool aok = m >= 0 && m < P.M && n < P.N;
-          int64_t am = m;
-          if (P.add_sh && aok) aok = addend_sub_row(P, m, am);
-          addv[it] = aok ? *reinterpret_cast<const uint4*>(P.ADD + am * P.ldc + n) : make_uint4(0u, 0u, 0u, 0u);
-        }
-      }
+    // fully unrolled, addend loads first: all of a thread's chunks are in flight together
+    // instead of one load -> add -> store round trip per chunk
+    uint4 addv[ITERS];
+    if (P.ADD) {
 #pragma unroll
       for (int it = 0; it < ITERS; ++it) {
         const int idx = it * THREADS + tid, row = idx / CH, ch = idx % CH;
         const int m = CLS ? rowpix[row] : m0 + row, n = n0 + ch * 8;
-        if (m >= 0 && m < P.M && n < P.N) {
-          uint4 v = *reinterpret_cast<const uint4*>(Cs + row * CS_LD + ch * 8);
-          if (EPIK == EPI_RELU && MODE == 1) {
-            v = gate_bf16x8(v, addv[it]);      // (the x tile: loaded above as the addend is)
-          } else if (P.ADD) {   // fused gradient accumulation: out = bf16(bf16(acc) + addend), as the separate add would give
-            const uint4 q = addv[it];
-            v.x = add_bf16x2(v.x, q.x); v.y = add_bf16x2(v.y, q.y); v.z = add_bf16x2(v.z, q.z); v.w = add_bf16x2(v.w, q.w);
-          }
-          if (EPIK == EPI_RELU && MODE == 0) v = relu_bf16x8(v);
-          store16(C + (int64_t)m * P.ldc + n, v);
-        }
-      }
-    } else {
-      // Batch-norm backward reductions fused into the dgrad epilogue (rigl_masked_conv2d_bwd_bn): the tile being stored
-      // IS the gradient w.r.t. y = relu?(bn(x) [+ residual]); sum dz and sum dz * xhat (dz = relu-masked gradient) per
-      // column are exactly what the batch norm's own reduction pass would read this tensor and x again for
-      // (bn.hip k_reduce<1>: resnet_model.py:41-82 through autodiff).  A thread owns one 8-column chunk for all its
-      // rows; the per-channel statistics sit in LDS behind the staging tile; the matching x tile was requested at the
-      // top of the kernel (stride-1 layers) and has long arrived.
-      const int chf = tid % CH;
-      const float* bprm = reinterpret_cast<const float*>(smem + PRM_OFF);   // [4][BN]: mean, invstd, scale, shift (filled at the top)
-      if (!PRM_OUT) {
-        float* bw = reinterpret_cast<float*>(smem + PRM_OFF);
-        for (int i = tid; i < 4 * BN; i += THREADS) {
-          const int k = i / BN, c = i % BN;
-          bw[i] = (n0 + c < P.N) ? P.BNP[k * P.N + n0 + c] : 0.f;
-        }
-        __syncthreads();
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) q0[j] = q1[j] = 0.f;
-      constexpr int BATCH = ITERS < 4 ? ITERS : 4;
-      static_assert(ITERS % BATCH == 0, "whole batches");
-#pragma unroll
-      for (int b0 = 0; b0 < ITERS; b0 += BATCH) {
-        uint4 addv[BATCH];
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-          const int idx = (b0 + u) * THREADS + tid, row = idx / CH, ch = idx % CH;
-          const int m = CLS ? rowpix[row] : m0 + row, n = n0 + ch * 8;
-          const bool ok = m >= 0 && m < P.M && n < P.N;
-          addv[u] = (P.ADD && ok) ? *reinterpret_cast<const uint4*>(P.ADD + (int64_t)m * P.ldc + n) : make_uint4(0u, 0u, 0u, 0u);
-          if constexpr (CLS) {      // class-major rows: the pixel table exists only now (batch by batch: register budget)
-            bnx[b0 + u] = ok ? *reinterpret_cast<const uint4*>(P.BNX + (int64_t)m * P.ldc + n) : make_uint4(0u, 0u, 0u, 0u);
-            bnb[b0 + u] = (ok && P.BNBITS) ? (uint32_t)P.BNBITS[((int64_t)m * P.ldc + n) >> 3] : 0u;
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-          const int it = b0 + u;
-          const int idx = it * THREADS + tid, row = idx / CH, ch = idx % CH;
-          const int m = CLS ? rowpix[row] : m0 + row, n = n0 + ch * 8;
-          if (m >= 0 && m < P.M && n < P.N) {
-            uint4 v = *reinterpret_cast<const uint4*>(Cs + row * CS_LD + ch * 8);
-            if (P.ADD) {
-              const uint4 q = addv[u];
-              v.x = add_bf16x2(v.x, q.x); v.y = add_bf16x2(v.y, q.y); v.z = add_bf16x2(v.z, q.z); v.w = add_bf16x2(v.w, q.w);
-            }
-            *reinterpret_cast<uint4*>(C + (int64_t)m * P.ldc + n) = v;
-            const uint32_t vw[4] = {v.x, v.y, v.z, v.w}, xw[4] = {bnx[it].x, bnx[it].y, bnx[it].z, bnx[it].w};
-            const float* pc = bprm + chf * 8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const float dv = __uint_as_float((j & 1) ? (vw[j >> 1] & 0xFFFF0000u) : (vw[j >> 1] << 16));
-              const float xv = __uint_as_float((j & 1) ? (xw[j >> 1] & 0xFFFF0000u) : (xw[j >> 1] << 16));
-              bool on = true;
-              if (P.bn_relu) on = P.BNBITS ? ((bnb[it] >> j) & 1u) != 0u : (fmaf(xv, pc[2 * BN + j], pc[3 * BN + j]) > 0.f);
-              const float dz = on ? dv : 0.f;
-              q0[j] += dz;
-              q1[j] = fmaf(dz, (xv - pc[j]) * pc[BN + j], q1[j]);
-            }
-          }
-        }
+        bool aok = m >= 0 && m < P.M && n < P.N;
+        int64_t am = m;
+        if (P.add_sh && aok) aok = addend_sub_row(P, m, am);
+        addv[it] = aok ? *reinterpret_cast<const uint4*>(P.ADD + am * P.ldc + n) : make_uint4(0u, 0u, 0u, 0u);
       }
     }
-    if (bnst) {
-      // Combine the row groups of every column chunk in a fixed order (deterministic): the lanes of a wave that share a
-      // chunk are CH apart (xor-shuffle tree), the four waves meet in the staging area every thread has finished reading.
 #pragma unroll
-      for (int off = CH; off < 64; off <<= 1) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { q0[j] += __shfl_xor(q0[j], off); q1[j] += __shfl_xor(q1[j], off); }
-      }
-      __syncthreads();
-      float* red = reinterpret_cast<float*>(smem);           // [waves][CH][16]
-      if (lane < CH) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { red[(wave * CH + lane) * 16 + j] = q0[j]; red[(wave * CH + lane) * 16 + 8 + j] = q1[j]; }
-      }
-      __syncthreads();
-      if (tid < CH * 16) {
-        const int c = tid >> 4, v = tid & 15;
-        float sum = red[c * 16 + v];
-#pragma unroll
-        for (int wv = 1; wv < THREADS / 64; ++wv) sum += red[(wv * CH + c) * 16 + v];
-        const int n = n0 + c * 8 + (v & 7);
-        if (n < P.N) P.STATS[(int64_t)tile_m * 2 * P.N + (int64_t)(v >> 3) * P.N + n] = sum;
+    for (int it = 0; it < ITERS; ++it) {
+      const int idx = it * THREADS + tid, row = idx / CH, ch = idx % CH;
+      const int m = CLS ? rowpix[row] : m0 + row, n = n0 + ch * 8;
+      if (m >= 0 && m < P.M && n < P.N) {
+        uint4 v = *reinterpret_cast<const uint4*>(Cs + row * CS_LD + ch * 8);
+        if (EPIK == EPI_RELU && MODE == 1) {
+          v = gate_bf16x8(v, addv[it]);      // (the x tile: loaded above as the addend is)
+        } else if (P.ADD) {   // fused gradient accumulation: out = bf16(bf16(acc) + addend), as the separate add would give
+          const uint4 q = addv[it];
+          v.x = add_bf16x2(v.x, q.x); v.y = add_bf16x2(v.y, q.y); v.z = add_bf16x2(v.z, q.z); v.w = add_bf16x2(v.w, q.w);
+        }
+        if (EPIK == EPI_RELU && MODE == 0) v = relu_bf16x8(v);
+        store16(C + (int64_t)m * P.ldc + n, v);
       }
     }
   }
@@ -1564,7 +1437,7 @@ static size_t pp_ksplit_workspace(const RiglConvDesc* d) {
 // dX.  The form of a call rules bodies out: this form admits these bodies.
 enum DxForm {
   DXF_PLAIN,    // every body
-  DXF_IGEMM,    // a batch-norm block, or a subsampled addend to the stand-alone dgrad: only the igemm epilogue takes them
+  DXF_IGEMM,    // a subsampled addend to the stand-alone dgrad: only the igemm epilogue takes it
   DXF_SUB,      // a subsampled addend inside the one-call backward: bwdslice (it rides in the same DMA ring: rows without
                 // an addend row read zeros), otherwise igemm
   DXF_GRID,     // the own-grid dgrad of rigl_masked_conv2d_bwd_grid: the shared launches only (ping-pong, igemm)
@@ -1839,31 +1712,6 @@ int rigl_masked_conv2d_fwd(const RiglConvDesc* d, const rigl_bf16* x, const rigl
   return rigl_masked_conv2d_fwd_stats(d, x, w_ohwi, y, nullptr, 0, workspace, workspace_bytes, stream);
 }
 
-// Which dgrad kernel a layer gets decides whether its epilogue can carry the batch-norm backward reductions: only
-// the igemm body does (the default for every cin % 8 == cout % 8 == 0 layer); returns its number of row tiles, else 0.
-int32_t rigl_conv2d_dgrad_stats_parts(const RiglConvDesc* d) {
-  using namespace rigl;
-  using namespace rigl::k1;
-  if (!d || check_desc(d, "rigl_conv2d_dgrad_stats_parts")) return 0;
-  if ((d->cin % 8) || (d->cout % 8)) return 0;
-  IgemmArgs a = dgrad_args(d, nullptr, nullptr, nullptr, nullptr);
-  if (select_dx(d, a).body != DX_IGEMM) return 0;     // the single-pass, row-streaming, c3x3 and ping-pong dgrads have no reduction epilogue
-  const IgemmPlan pl = plan_igemm<1>(a);
-  return (int32_t)(pl.grid / (unsigned)a.tiles_n);
-}
-
-static int attach_bn(rigl::k1::IgemmArgs& a, const RiglConvDesc* d, const RiglBnReduceFuse* bn) {
-  using namespace rigl;
-  if (!bn) return RIGL_OK;
-  if (!bn->x || !bn->params || !bn->partial) return fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd_bn: NULL pointer in the batch-norm block");
-  const int32_t parts = rigl_conv2d_dgrad_stats_parts(d);
-  if (parts <= 0) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_bn: this layer's dgrad kernel has no reduction epilogue");
-  if (bn->partial_floats < (size_t)parts * 2 * d->cin)
-    return fail(RIGL_EWORKSPACE, "rigl_masked_conv2d_bwd_bn: partial buffer %zu floats < %zu", bn->partial_floats, (size_t)parts * 2 * d->cin);
-  a.BNX = bn->x; a.BNBITS = bn->relu_bits; a.BNP = bn->params; a.bn_relu = bn->relu; a.STATS = bn->partial;
-  return RIGL_OK;
-}
-
 // The addend of a dgrad may be the gradient of a SUBSAMPLED view of the tensor (sh, sw > 1: one row per pixel with
 // h % sh == 0 and w % sw == 0); only the igemm body's epilogue takes that form, so such a call stays on it.
 struct AddendSub { int sh, sw; };
@@ -1876,7 +1724,7 @@ static void set_addend_sub(rigl::k1::IgemmArgs& a, const RiglConvDesc* d, Addend
 // epi = EPI_RELU (rigl_masked_conv2d_bwd_relu, only where relu_dgrad_fusable): `addend` is the conv's input x, whose sign
 // gates dX in the igemm / ping-pong dgrad epilogue
 static int dgrad_impl(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio, const rigl_bf16* addend,
-                      rigl_bf16* dx, const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub = {1, 1},
+                      rigl_bf16* dx, rigl_stream_t stream, AddendSub sub = {1, 1},
                       int epi = rigl::k1::EPI_NONE) {
   using namespace rigl;
   using namespace rigl::k1;
@@ -1889,12 +1737,9 @@ static int dgrad_impl(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf1
   prof_set_tag(d);
   ProfFamily prof(PROF_CONV_DGRAD);
   const bool subadd = addend_is_sub(addend, sub);
-  if (subadd && bn) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_dgrad: a subsampled addend and the batch-norm reductions do not combine");
   IgemmArgs a = dgrad_args(d, dy, w_hwio, addend, dx);
   if (subadd) set_addend_sub(a, d, sub);
-  rc = attach_bn(a, d, bn);
-  if (rc) return rc;
-  const DxForm form = bn || subadd ? DXF_IGEMM : DXF_PLAIN;
+  const DxForm form = subadd ? DXF_IGEMM : DXF_PLAIN;
   DxSel s = select_dx(d, a, form);
   // the big-M 1x1 layers: dX from the single-pass backward kernel (without its weight-gradient half), so that it has the
   // bits rigl_masked_conv2d_bwd gives it
@@ -1919,7 +1764,7 @@ int rigl_masked_conv2d_dgrad_acc(const RiglConvDesc* d, const rigl_bf16* dy, con
                                  const rigl_bf16* addend, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
                                  rigl_stream_t stream) {
   (void)workspace; (void)workspace_bytes;
-  return dgrad_impl(d, dy, w_hwio, addend, dx, nullptr, stream);
+  return dgrad_impl(d, dy, w_hwio, addend, dx, stream);
 }
 
 int rigl_masked_conv2d_dgrad(const RiglConvDesc* d, const rigl_bf16* dy, const rigl_bf16* w_hwio, rigl_bf16* dx,
@@ -2014,7 +1859,7 @@ int rigl_masked_conv2d_wgrad(const RiglConvDesc* d, const rigl_bf16* x, const ri
 
 static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
                     const rigl_bf16* addend, float* dw, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
-                    const RiglBnReduceFuse* bn, rigl_stream_t stream, AddendSub sub = {1, 1},
+                    rigl_stream_t stream, AddendSub sub = {1, 1},
                     const RiglConvDesc* dg = nullptr, const uint8_t* addend_bits = nullptr, int epi = rigl::k1::EPI_NONE) {
   // dg (rigl_masked_conv2d_bwd_grid): the dgrad half runs on THIS descriptor -- the stride-1 twin of a strided 1x1 conv
   // on its own output grid -- while the weight gradient reads x through d; the two halves of the shared launch take
@@ -2029,14 +1874,13 @@ static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* 
   hipStream_t st = as_stream(stream);
   prof_set_tag(d);
   const bool subadd = addend_is_sub(addend, sub);
-  if (subadd && bn) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd: a subsampled addend and the batch-norm reductions do not combine");
   if (subadd && !dx) return fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd: an addend without dX");
   const size_t need = rigl_conv2d_workspace_bytes(d, 2);
   float* const slabs = static_cast<float*>(workspace);
   // Both gradients asked for, every operand there: the bodies that compute dX and dW in one call.  Each checks the
   // workspace before its first launch.
   if (dx && x && dy && w_hwio && dw) {
-    const DxForm form = bn ? DXF_IGEMM : subadd ? DXF_SUB : dg ? DXF_GRID : addend_bits ? DXF_MASKED : DXF_PLAIN;
+    const DxForm form = subadd ? DXF_SUB : dg ? DXF_GRID : addend_bits ? DXF_MASKED : DXF_PLAIN;
     IgemmArgs ad = dgrad_args(dd, dy, w_hwio, addend, dx);
     DxSel s = select_dx(dd, ad, form);
     if (s.body == DX_BWD1X1) {
@@ -2094,8 +1938,6 @@ static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* 
     // except the own-grid form, which has no stand-alone twin to agree with.
     if ((s.body == DX_IGEMM || (s.body == DX_PP && dg)) && fuse && (d->cin % 8) == 0 && (d->cout % 8) == 0) {
       if (subadd) set_addend_sub(ad, dd, sub);
-      rc = attach_bn(ad, d, bn);
-      if (rc) return rc;
       const IgemmPlan pd = plan_igemm<1>(ad);
       // (launched alone back to back, a large short-reduction dgrad -- the 56x56 / 28x28 1x1 "reduce" convs -- is 9-28 %
       // slower when it shares the launch, the other layers 3-10 % faster; inside the training step sharing always won)
@@ -2127,16 +1969,7 @@ static int bwd_impl(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* 
     return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_masked: this layer's kernels take no masked addend (ask rigl_conv2d_bwd_takes_masked_addend)");
   rc = wgrad_impl(d, x, dy, dw, workspace, workspace_bytes, stream, PROF_CONV_WGRAD);
   if (rc || !dx) return rc;
-  return dgrad_impl(dd, dy, w_hwio, addend, dx, bn, stream, sub, epi);
-}
-
-// rigl_masked_conv2d_bwd with the batch-norm backward reductions of the tensor dX is the gradient of riding in the dgrad
-// epilogue.
-int rigl_masked_conv2d_bwd_bn(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
-                              const rigl_bf16* addend, float* dw, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
-                              const RiglBnReduceFuse* bn, rigl_stream_t stream) {
-  if (bn && !dx) return rigl::fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd_bn: the reductions ride on dX, which was not requested");
-  return bwd_impl(d, x, dy, w_hwio, addend, dw, dx, workspace, workspace_bytes, bn, stream);
+  return dgrad_impl(dd, dy, w_hwio, addend, dx, stream, sub, epi);
 }
 
 // Backward of y = relu(conv(x, w)) where x is itself the output of a ReLU (or a max pool of one) and dy arrives already
@@ -2159,8 +1992,8 @@ int rigl_masked_conv2d_bwd_relu(const RiglConvDesc* d, const rigl_bf16* x, const
   if (!x || !dy || !w_hwio || !dw || !dx) return fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd_relu: NULL tensor");
   if ((d->cin % 8) || (d->cout % 8)) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_relu: cin/cout %% 8 != 0");
   if (relu_dgrad_fusable(d))
-    return bwd_impl(d, x, dy, w_hwio, x, dw, dx, workspace, workspace_bytes, nullptr, stream, AddendSub{1, 1}, nullptr, nullptr, EPI_RELU);
-  rc = bwd_impl(d, x, dy, w_hwio, nullptr, dw, dx, workspace, workspace_bytes, nullptr, stream);
+    return bwd_impl(d, x, dy, w_hwio, x, dw, dx, workspace, workspace_bytes, stream, AddendSub{1, 1}, nullptr, nullptr, EPI_RELU);
+  rc = bwd_impl(d, x, dy, w_hwio, nullptr, dw, dx, workspace, workspace_bytes, stream);
   if (rc) return rc;
   return relu_bwd_launch((int64_t)d->n * d->h * d->w * d->cin, dx, x, dx, as_stream(stream));
 }
@@ -2172,7 +2005,7 @@ int rigl_masked_conv2d_bwd_relu(const RiglConvDesc* d, const rigl_bf16* x, const
 int rigl_masked_conv2d_bwd(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
                            const rigl_bf16* addend, float* dw, rigl_bf16* dx, void* workspace, size_t workspace_bytes,
                            rigl_stream_t stream) {
-  return bwd_impl(d, x, dy, w_hwio, addend, dw, dx, workspace, workspace_bytes, nullptr, stream);
+  return bwd_impl(d, x, dy, w_hwio, addend, dw, dx, workspace, workspace_bytes, stream);
 }
 
 // rigl_masked_conv2d_bwd whose addend arrives UNMASKED together with a 1-bit-per-element mask (bit set = the addend counts):
@@ -2232,7 +2065,7 @@ int rigl_masked_conv2d_bwd_masked(const RiglConvDesc* d, const rigl_bf16* x, con
                                   const rigl_bf16* addend, const uint8_t* addend_bits, float* dw, rigl_bf16* dx,
                                   void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
   if (!addend || !addend_bits || !dx) return rigl::fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd_masked: addend, addend_bits and dx are required");
-  return bwd_impl(d, x, dy, w_hwio, addend, dw, dx, workspace, workspace_bytes, nullptr, stream, AddendSub{1, 1}, nullptr, addend_bits);
+  return bwd_impl(d, x, dy, w_hwio, addend, dw, dx, workspace, workspace_bytes, stream, AddendSub{1, 1}, nullptr, addend_bits);
 }
 
 // rigl_masked_conv2d_bwd whose addend is the gradient of a SUBSAMPLED view of the conv's input: [n][ceil(h / sub_h)][ceil(w /
@@ -2255,14 +2088,14 @@ int rigl_masked_conv2d_bwd_grid(const RiglConvDesc* d, const rigl_bf16* x, const
   if ((d->cin % 8) || (d->cout % 8)) return fail(RIGL_EUNSUPPORTED, "rigl_masked_conv2d_bwd_grid: cin/cout %% 8 != 0");
   RiglConvDesc g = *d;
   g.h = d->ho; g.w = d->wo; g.stride_h = g.stride_w = 1;
-  return bwd_impl(d, x, dy, w_hwio, nullptr, dw, dx_grid, workspace, workspace_bytes, nullptr, stream, AddendSub{1, 1}, &g);
+  return bwd_impl(d, x, dy, w_hwio, nullptr, dw, dx_grid, workspace, workspace_bytes, stream, AddendSub{1, 1}, &g);
 }
 
 int rigl_masked_conv2d_bwd_sub(const RiglConvDesc* d, const rigl_bf16* x, const rigl_bf16* dy, const rigl_bf16* w_hwio,
                                const rigl_bf16* addend, int32_t sub_h, int32_t sub_w, float* dw, rigl_bf16* dx,
                                void* workspace, size_t workspace_bytes, rigl_stream_t stream) {
   if (sub_h < 1 || sub_w < 1) return rigl::fail(RIGL_EINVAL, "rigl_masked_conv2d_bwd_sub: subsampling factors must be >= 1");
-  return bwd_impl(d, x, dy, w_hwio, addend, dw, dx, workspace, workspace_bytes, nullptr, stream, AddendSub{sub_h, sub_w});
+  return bwd_impl(d, x, dy, w_hwio, addend, dw, dx, workspace, workspace_bytes, stream, AddendSub{sub_h, sub_w});
 }
 
 

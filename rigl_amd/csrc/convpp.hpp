@@ -693,7 +693,6 @@ static bool pp_legal(const IgemmArgs& a, int variant) {
   if (a.N % bn) return false;
   if (a.KH * a.KW > 32) return false;
   if (MODE == 1 && (a.sh > 2 || a.sw > 2)) return false;     // strided dgrad: parity classes, strides <= 2 like igemm_body
-  if (a.BNX) return false;
   if (a.M < bm) return false;
   return true;
 }
@@ -705,7 +704,7 @@ static int pp_bwd_dgrad_variant(const IgemmArgs& a) {
   if (pp_bwd == 0) return PP_NONE;
   const int64_t m_out = (int64_t)(a.M / (a.RH * a.RW)) * a.GH * a.GW;
   // the weight gradient that shares the launch has 256-channel tiles: cin (= N here) and cout (= Cred) multiples of 256
-  if (a.N % 256 || a.Cred % 256 || m_out < 256 || a.KH * a.KW > 32 || a.BNX || a.sh > 2 || a.sw > 2) return PP_NONE;
+  if (a.N % 256 || a.Cred % 256 || m_out < 256 || a.KH * a.KW > 32 || a.sh > 2 || a.sw > 2) return PP_NONE;
   if (pp_bwd > 0) return pp_bwd == 2 ? PP_128x256 : PP_256x256;
   // built-in rule (tools/pp_sweep.py --passes bwd, batch 128): dgrad reductions of >= 16 K-tiles (a strided dgrad: its
   // longest parity class, ceil(KH / sh) x ceil(KW / sw) taps); 256x256 dgrad tiles where they give at least ~1/3 of the

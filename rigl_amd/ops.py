@@ -759,13 +759,6 @@ def conv_wgrad(d, x, dy, dw=None, force_ref=False):
   return dw
 
 
-def dgrad_stats_parts(d):
-  """Row tiles of this layer's dgrad kernel = rows of the batch-norm partials its epilogue can leave
-  (0: the layer's dgrad has no such epilogue)."""
-  v = _plan_cached(d, 'dgrad_parts', lambda: int(_lib.load().rigl_conv2d_dgrad_stats_parts(C.byref(d))))
-  return v
-
-
 def conv_bwd_takes_masked_addend(d):
   """Should the producer of this layer's addend hand it over unmasked + a 1-bit mask (rigl_masked_conv2d_bwd_masked) instead
   of writing the masked copy?  (rigl_conv2d_bwd_takes_masked_addend: the layers whose default selection has the masked form.)"""
@@ -831,15 +824,12 @@ def conv_bwd_bnapply(d, x, dout, w_hwio, dw, y, relu_bits, saved, coef, addend=N
       _ptr(saved[0]), _ptr(saved[1]), _ptr(coef), _stream()))
 
 
-def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, bn_fuse=None, addend_sub=None,
-             addend_bits=None, dx=None):
+def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, addend_sub=None, addend_bits=None,
+             dx=None):
   """dW (into ``dw``, dense fp32) and -- when ``need_dx`` -- dX (+ ``addend``) of one conv with a single host
   transition and, for ordinary layers, a single launch (rigl_masked_conv2d_bwd) followed by the split-K reduce that
   completes dW.  ``on_dw_ready`` is called once dW's last kernel has been enqueued (the data-parallel exchange launches
   its buckets from there).  Returns dX or None.
-  ``bn_fuse`` = dict(x=, saved=, relu=, relu_bits=) of the batch norm whose output this conv read: its backward
-  reductions are computed in the dgrad epilogue (rigl_masked_conv2d_bwd_bn) and returned as
-  ``bn_fuse['partials']`` (fp32 [parts, 2, Cin]) for bn_bwd; left unset where the layer's kernels cannot.
   ``addend_sub`` = (sh, sw): ``addend`` is the gradient of the subsampled view x[:, ::sh, ::sw, :] -- bf16
   [n, ceil(h / sh), ceil(w / sw), cin] -- added at those pixels only (rigl_masked_conv2d_bwd_sub).
   ``addend_bits`` (uint8, one bit per element of ``addend``): the addend counts only where its bit is set
@@ -848,24 +838,19 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
   if addend_sub is not None and tuple(addend_sub) == (1, 1):
     addend_sub = None
   n_in = d.n * d.h * d.w * d.cin
-  both = mfma_supported(d) and mfma_dgrad_supported(d)
   if addend_bits is not None:
-    if addend is None or not need_dx or bn_fuse is not None or addend_sub is not None:
-      raise ValueError('addend_bits needs an addend and dX, and combines with neither bn_fuse nor addend_sub')
+    if addend is None or not need_dx or addend_sub is not None:
+      raise ValueError('addend_bits needs an addend and dX, and does not combine with addend_sub')
     _req(addend, torch.bfloat16, 'addend'); _req(addend_bits, torch.uint8, 'addend_bits')
     if addend.numel() != n_in or addend_bits.numel() * 8 != n_in:
       raise ValueError('addend must have the shape of dx and addend_bits one bit per element of it')
     return _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_bwd_masked(
         C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), _ptr(addend_bits), _ptr(dw), pdx, ws, nws, _stream()))
   if addend_sub is not None:
-    if addend is None or not need_dx or bn_fuse is not None:
-      raise ValueError('addend_sub needs an addend and dX, and does not combine with bn_fuse')
-    if not both:
+    if addend is None or not need_dx:
+      raise ValueError('addend_sub needs an addend and dX')
+    if not (mfma_supported(d) and mfma_dgrad_supported(d)):
       raise ValueError('addend_sub needs cin % 8 == cout % 8 == 0')
-  if bn_fuse is not None:
-    bn_fuse.pop('partials', None)
-    if not (need_dx and both and dgrad_stats_parts(d) > 0):
-      bn_fuse = None
   if not (mfma_supported(d) and (not need_dx or mfma_dgrad_supported(d))):
     conv_wgrad(d, x, dy, dw)
     if on_dw_ready is not None:
@@ -880,21 +865,8 @@ def conv_bwd(d, x, dy, w_hwio, dw, need_dx=True, addend=None, on_dw_ready=None, 
         C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), int(sh), int(sw), _ptr(dw), pdx, ws, nws, _stream()))
   if need_dx and addend is not None and addend.numel() != n_in:
     raise ValueError('addend must have the shape of dx')
-  bn = None
-  if bn_fuse is not None:
-    bx, saved = bn_fuse['x'], bn_fuse['saved']
-    _req(bx, torch.bfloat16, 'bn x')
-    _req(saved, torch.float32, 'bn saved')
-    bits = bn_fuse.get('relu_bits')
-    _req(bits, torch.uint8, 'bn relu_bits', allow_none=True)
-    if bx.numel() != n_in or saved.numel() != 4 * d.cin:
-      raise ValueError('bn_fuse: x must have the shape of dx and saved must be [4, Cin]')
-    part = torch.empty((dgrad_stats_parts(d), 2, d.cin), dtype=torch.float32, device=dy.device)
-    bn = C.byref(_lib.BnReduceFuse(bx.data_ptr(), bits.data_ptr() if bits is not None else None, saved.data_ptr(),
-                                   int(bool(bn_fuse['relu'])), part.data_ptr(), part.numel()))
-    bn_fuse['partials'] = part
-  return _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_bwd_bn(
-      C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), _ptr(dw), pdx, ws, nws, bn, _stream()), need_dx=need_dx)
+  return _conv_bwd(d, x, dy, w_hwio, dw, dx, on_dw_ready, lambda lib, pdx, ws, nws: lib.rigl_masked_conv2d_bwd(
+      C.byref(d), _ptr(x), _ptr(dy), _ptr(w_hwio), _ptr(addend), _ptr(dw), pdx, ws, nws, _stream()), need_dx=need_dx)
 
 
 def conv_bwd_grid(d, x, dy, w_hwio, dw, on_dw_ready=None, dx=None):
@@ -1049,9 +1021,9 @@ def depthwise_wgrad(d, x, dy, dw):
 # ----------------------------------------------------------------------------
 # fused batch-norm (+ residual) (+ ReLU)
 # ----------------------------------------------------------------------------
-def _bn_plan(x, partials=None, need_ws=False):
+def _bn_plan(x, partials=None):
   """(rows, channels, workspace or None, parts) of a batch-norm call over the channel axis of bf16 ``x``: ``partials`` (checked:
-  fp32 [parts, 2, C]) stand in for the statistics pass, so the reduction workspace is only fetched without them or on ``need_ws``."""
+  fp32 [parts, 2, C]) stand in for the statistics pass, so the reduction workspace is only fetched without them."""
   _req(x, torch.bfloat16, 'x')
   c = x.shape[-1]
   m = x.numel() // c
@@ -1061,7 +1033,7 @@ def _bn_plan(x, partials=None, need_ws=False):
     if partials.dim() != 3 or partials.shape[1] != 2 or partials.shape[2] != c:
       raise ValueError('partials must be [parts, 2, %d]' % c)
     parts = partials.shape[0]
-  ws = workspace(_lib.load().rigl_bn_workspace_bytes(m, c), x.device) if (need_ws or partials is None) else None
+  ws = workspace(_lib.load().rigl_bn_workspace_bytes(m, c), x.device) if partials is None else None
   return m, c, ws, parts
 
 
@@ -1090,23 +1062,20 @@ def bn_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, relu,
 
 
 def bn_bwd(x, y, dy, gamma, saved, relu, dgamma, dbeta, want_dres=False,
-           relu_bits=None, partials=None):
+           relu_bits=None):
   """Returns (dx, dres|None); dgamma / dbeta (fp32 [C]) are overwritten.  The
   ReLU mask comes from ``relu_bits`` (bn_fwd(want_relu_bits=True)), else ``y``,
-  else it is recomputed from x.  ``partials`` (fp32 [parts, 2, C]: sum dz, sum dz * xhat per row
-  tile, left by the dgrad epilogue that produced ``dy`` -- conv_bwd(bn_fuse=...)) replaces the
-  reduction pass over dy and x."""
+  else it is recomputed from x."""
   _req(relu_bits, torch.uint8, 'relu_bits', allow_none=True)
   _req(dy, torch.bfloat16, 'dy')
   _req(y, torch.bfloat16, 'y', allow_none=True)
-  m, c, ws, parts = _bn_plan(x, partials, need_ws=True)
+  m, c, ws, _ = _bn_plan(x)
   dx = torch.empty_like(x)
   dres = torch.empty_like(x) if want_dres else None
-  check(_lib.load().rigl_bn_bwd_stats(m, c, _ptr(x), _ptr(y), _ptr(relu_bits), _ptr(dy), _ptr(gamma),
-                                      _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]),
-                                      _ptr(saved[3]), int(bool(relu)), _ptr(dx), _ptr(dres),
-                                      _ptr(dgamma), _ptr(dbeta), _ptr(partials), parts, _ptr(ws), ws.numel(),
-                                      _stream()))
+  check(_lib.load().rigl_bn_bwd(m, c, _ptr(x), _ptr(y), _ptr(relu_bits), _ptr(dy), _ptr(gamma),
+                                _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]),
+                                _ptr(saved[3]), int(bool(relu)), _ptr(dx), _ptr(dres),
+                                _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(), _stream()))
   return dx, dres
 
 

@@ -36,38 +36,9 @@ def _valid_out(size, k, stride):
   return (size - k) // stride + 1
 
 
-# RIGL_BN_FUSE_BWD=1: a batch norm's backward reductions ride in the dgrad epilogue of its output's only consumer
-# (rigl_masked_conv2d_bwd_bn).  OFF by default: measured on ResNet-50 at batch 128 the reduction pass it removes costs
-# 10-17 us per layer and the epilogue work it adds 15-19 us (profiles/r2/README.md) -- 13.29 vs 13.30 ms per step
-# with K1's share of it up by 1 ms.
-_BN_FUSE_BWD = os.environ.get('RIGL_BN_FUSE_BWD', '0') == '1'
 # RIGL_CONV_PAIR=0: the first block of a group runs projection and conv1 as two autograd nodes (read once; tests override
-# the module attribute).  The pair node carries no batch-norm holder: with RIGL_BN_FUSE_BWD=1 it steps aside for the fork path.
+# the module attribute).
 _CONV_PAIR = os.environ.get('RIGL_CONV_PAIR', '1') != '0'
-# ... only for activations of at most this many MB (the large early tensors make the dgrad launch HBM-bound already)
-_BN_FUSE_MAX_BYTES = float(os.environ.get('RIGL_BN_FUSE_MAX_MB', '1e9')) * 1e6
-
-
-def _bn_source(x):
-  """The batch norm that produced ``x`` (workloads.nn.BatchNorm leaves a holder on its output): its backward
-  reductions can ride in this conv's dgrad epilogue.  Counted, because that is only right for the SOLE consumer."""
-  h = getattr(x, 'bn_ctx', None) if _BN_FUSE_BWD else None
-  if h is not None:
-    h.attached += 1
-  return h
-
-
-def _bn_fuse_request(holder, need_dx):
-  if holder is None or not need_dx or holder.attached != 1 or holder.x is None:
-    return None
-  if holder.x.numel() * 2 > _BN_FUSE_MAX_BYTES:
-    return None
-  return dict(x=holder.x, saved=holder.saved, relu=holder.relu, relu_bits=holder.bits)
-
-
-def _bn_fuse_publish(holder, req, dx):
-  if req is not None and req.get('partials') is not None and dx is not None:
-    holder.partials, holder.dx_ptr = req['partials'], dx.data_ptr()
 
 
 class _HandOver:
@@ -158,9 +129,8 @@ class _MaskedConvFn(torch.autograd.Function):
   """y = conv(x, mask*W) with dense dW written into lv.weights.grad."""
 
   @staticmethod
-  def forward(ctx, x, lv, desc, need_dx, want_stats=False, bn_holder=None, pending=None, apply_holder=None):
-    ctx.lv, ctx.desc, ctx.need_dx = lv, desc, need_dx
-    ctx.bn_holder, ctx.apply_holder = bn_holder, apply_holder
+  def forward(ctx, x, lv, desc, need_dx, want_stats=False, pending=None, apply_holder=None):
+    ctx.lv, ctx.desc, ctx.need_dx, ctx.apply_holder = lv, desc, need_dx, apply_holder
     ctx.save_for_backward(x)
     if pending is not None:
       # x is the still EMPTY output of a batch norm that only finalised its statistics (workloads.nn.BatchNorm, consumer=):
@@ -181,16 +151,14 @@ class _MaskedConvFn(torch.autograd.Function):
     if x.dtype == torch.float32:
       dx = ops.conv_bwd_f32(d, x, dy, lv.weights.data.view(-1), _mask_bits(lv), lv.weights.grad.view(-1),
                             need_dx=ctx.need_dx, on_dw_ready=ready)
-      return (dx,) + (None,) * 7
+      return (dx,) + (None,) * 6
     got = ctx.apply_holder.take(dy) if ctx.apply_holder is not None else None
     if got is not None:
       # dy is the gradient w.r.t. the OUTPUT of the batch norm behind this conv: its apply pass runs on this backward's dY load
       dx = ops.conv_bwd_bnapply(d, x, dy, lv.hwio, lv.weights.grad.view(-1), *got, on_dw_ready=ready)
-      return (dx,) + (None,) * 7
-    req = _bn_fuse_request(ctx.bn_holder, ctx.need_dx)
-    dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=ctx.need_dx, on_dw_ready=ready, bn_fuse=req)
-    _bn_fuse_publish(ctx.bn_holder, req, dx)
-    return (dx,) + (None,) * 7
+      return (dx,) + (None,) * 6
+    dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=ctx.need_dx, on_dw_ready=ready)
+    return (dx,) + (None,) * 6
 
 
 class _MaskedConvReluFn(torch.autograd.Function):
@@ -229,9 +197,8 @@ class _MaskedConvForkFn(torch.autograd.Function):
   separate AddN pass autodiff would emit (rigl_masked_conv2d_dgrad_acc)."""
 
   @staticmethod
-  def forward(ctx, x, lv, desc, want_stats=False, bn_holder=None, addend_holder=None):
-    ctx.lv, ctx.desc = lv, desc
-    ctx.bn_holder, ctx.addend_holder = bn_holder, addend_holder
+  def forward(ctx, x, lv, desc, want_stats=False, addend_holder=None):
+    ctx.lv, ctx.desc, ctx.addend_holder = lv, desc, addend_holder
     ctx.save_for_backward(x)
     y, part = _conv_forward(lv, desc, x, want_stats)
     return stats_outputs(ctx, want_stats, (y, x.view_as(x)), (part,), x.device)
@@ -246,20 +213,16 @@ class _MaskedConvForkFn(torch.autograd.Function):
     if x.dtype == torch.float32:
       dx = ops.conv_bwd_f32(d, x, dy, lv.weights.data.view(-1), _mask_bits(lv), lv.weights.grad.view(-1),
                             need_dx=True, addend=dalias, on_dw_ready=ready)
-      return (dx,) + (None,) * 5
+      return (dx,) + (None,) * 4
     # the alias' gradient may arrive unmasked with the ReLU bits it still has to pass (workloads.nn._FusedBNFn): only as the very
     # tensor the batch norm handed over -- anything else (autograd summed or copied it) raises instead of being added unmasked
     got = ctx.addend_holder.take(dalias) if ctx.addend_holder is not None else None
     if got is not None:
       dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=True, addend=dalias, addend_bits=got[0],
                         on_dw_ready=ready)
-      return (dx,) + (None,) * 5
-    # dx = this conv's dgrad + the alias' gradient is the COMPLETE gradient of the forked tensor: the producing batch
-    # norm's reductions are taken on it
-    req = _bn_fuse_request(ctx.bn_holder, True)
-    dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=True, addend=dalias, on_dw_ready=ready, bn_fuse=req)
-    _bn_fuse_publish(ctx.bn_holder, req, dx)
-    return (dx,) + (None,) * 5
+      return (dx,) + (None,) * 4
+    dx = ops.conv_bwd(d, x, dy, lv.hwio, lv.weights.grad.view(-1), need_dx=True, addend=dalias, on_dw_ready=ready)
+    return (dx,) + (None,) * 4
 
 
 class _MaskedConvPairFn(torch.autograd.Function):
@@ -298,7 +261,7 @@ def conv_pair(conv_sub, conv_main, x, bn_stats=False):
   ok = (x.dtype == torch.bfloat16 and x.requires_grad and conv_sub.need_input_grad and conv_main.need_input_grad
         and conv_sub.kh == conv_sub.kw == 1 and max(conv_sub.strides) > 1
         and conv_sub.cin % 8 == 0 and conv_sub.units % 8 == 0 and conv_main.units % 8 == 0
-        and _CONV_PAIR and not (_BN_FUSE_BWD and getattr(x, 'bn_ctx', None) is not None))
+        and _CONV_PAIR)
   d_s = conv_sub.desc_for(n, h, w) if ok else None
   if ok and (d_s.pad_top or d_s.pad_left or d_s.ho != -(-h // d_s.stride_h) or d_s.wo != -(-w // d_s.stride_w)):
     ok = False
@@ -391,7 +354,6 @@ class MaskedConv2d(_Layer):
     n, h, w, _ = x.shape
     d = self.desc_for(n, h, w)
     need_dx = self.need_input_grad and x.requires_grad
-    holder = _bn_source(x) if need_dx else None
     pending = getattr(x, 'bn_pending', None)   # the batch norm in front left its apply pass to this conv (takes_bn_input)
     if pending is not None and (pending.x is None or not x.is_contiguous()):
       raise RuntimeError('a deferred batch-norm output must reach its consumer conv as it was returned')
@@ -400,9 +362,9 @@ class MaskedConv2d(_Layer):
     # the batch norm behind this conv may leave its backward apply pass to this conv's backward (workloads.nn.BatchNorm)
     apply_holder = BnApplyHolder() if (need_dx and x.dtype == torch.bfloat16 and x.is_cuda and ops.conv_bwd_takes_bn_apply(d)) else None
     if not bn_stats:
-      y = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, False, holder, pending, apply_holder)
+      y = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, False, pending, apply_holder)
     else:
-      y, part = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, True, holder, pending, apply_holder)
+      y, part = _MaskedConvFn.apply(x.contiguous(), self.vars, d, need_dx, True, pending, apply_holder)
       if part.numel():
         y.bn_partials = part
     if apply_holder is not None and y.grad_fn is not None:
@@ -435,7 +397,7 @@ class MaskedConv2d(_Layer):
   def takes_masked_addend(self, x):
     """Can the gradient of ``fork(x)``'s alias be handed to this conv unmasked with a 1-bit mask (rigl_masked_conv2d_bwd_masked)?
     Only then may the alias' other consumer (relu(bn3 + alias)) skip writing the masked gradient."""
-    if not (self.need_input_grad and x.requires_grad and x.dtype == torch.bfloat16 and x.dim() == 4) or _BN_FUSE_BWD:
+    if not (self.need_input_grad and x.requires_grad and x.dtype == torch.bfloat16 and x.dim() == 4):
       return False
     n, h, w, _ = x.shape
     return ops.conv_bwd_takes_masked_addend(self.desc_for(n, h, w))
@@ -449,10 +411,9 @@ class MaskedConv2d(_Layer):
       return self(x, bn_stats), x
     self.graph.refresh_shadows()
     n, h, w, _ = x.shape
-    holder = _bn_source(x)
     # relu(bn + alias) may hand the alias' gradient back unmasked with the ReLU bits (workloads.nn.BatchNorm arms this)
     addend_holder = MaskedAddendHolder() if self.takes_masked_addend(x) else None
-    y, alias, *part = _MaskedConvForkFn.apply(x.contiguous(), self.vars, self.desc_for(n, h, w), bn_stats, holder, addend_holder)
+    y, alias, *part = _MaskedConvForkFn.apply(x.contiguous(), self.vars, self.desc_for(n, h, w), bn_stats, addend_holder)
     if part and part[0].numel():
       y.bn_partials = part[0]
     if addend_holder is not None:

@@ -41,15 +41,13 @@ def nhwc_view(x):
   return x.permute(0, 2, 3, 1)
 
 
-class _BnBwdHolder:
-  """What the consumer of a batch norm's output needs to take that batch norm's backward reductions in its own dgrad
-  epilogue (pruning_layers._bn_source), and where it leaves them for the batch norm's backward."""
-  __slots__ = ('x', 'saved', 'bits', 'relu', 'attached', 'partials', 'dx_ptr')
+class _BnPending:
+  """What the conv behind a batch norm whose forward only finalised its statistics needs to apply it on its operand load
+  (MaskedConv2d reads it from its input's ``bn_pending``): the batch norm's input and its saved statistics."""
+  __slots__ = ('x', 'saved')
 
-  def __init__(self, relu):
-    self.x = self.saved = self.bits = self.partials = self.dx_ptr = None
-    self.relu = relu
-    self.attached = 0
+  def __init__(self):
+    self.x = self.saved = None
 
 
 _LAZY_RES_GRAD = os.environ.get('RIGL_LAZY_RES_GRAD', '1') != '0'
@@ -64,13 +62,13 @@ class _FusedBNFn(torch.autograd.Function):
   the conv kernels' dW; autograd only routes dx (and the residual's grad)."""
 
   @staticmethod
-  def forward(ctx, x, residual, bn, relu, partials=None, holder=None, addend_holder=None, defer=False, apply_holder=None):
+  def forward(ctx, x, residual, bn, relu, partials=None, pending=None, addend_holder=None, apply_holder=None):
     from rigl_amd import ops  # pylint: disable=import-outside-toplevel
     x_in = x
     x = x.contiguous()
     res = residual.contiguous() if residual is not None else None
     ctx.bn, ctx.relu, ctx.has_res = bn, relu, res is not None
-    ctx.holder = holder
+    ctx.pending, defer = pending, pending is not None
     # the residual is the alias of a conv's fork whose backward masks its addend on the fly (pruning_layers.MaskedAddendHolder,
     # left on the alias): the backward then returns the output gradient itself, unmasked, as the residual's and fills the
     # holder with the ReLU bits; decided (armed) here, and the fork's backward checks it
@@ -86,11 +84,11 @@ class _FusedBNFn(torch.autograd.Function):
       apply_holder.armed = True
     if defer:
       # statistics only: the consumer conv applies the batch norm + ReLU on its operand load and FILLS y as a side output
-      # (MaskedConv2d picks x and saved up from the holder: y.bn_pending)
+      # (MaskedConv2d picks x and saved up from y.bn_pending)
       saved = ops.bn_statistics(x, bn.gamma.data, bn.beta.data, bn.moving_mean, bn.moving_variance, 1.0 - bn.decay, bn.eps,
                                 partials=partials)
       ctx.save_for_backward(x, saved)
-      holder.x, holder.saved, holder.bits = x, saved, None
+      pending.x, pending.saved = x, saved
       return torch.empty_like(x)
     # the ReLU mask of relu(bn + residual) is kept as 1 bit per element (the backward would
     # otherwise re-read the whole output twice); without a residual it is recomputed from x
@@ -105,8 +103,6 @@ class _FusedBNFn(torch.autograd.Function):
                             bn.moving_variance, 1.0 - bn.decay, bn.eps, relu, res,
                             partials=partials)
       ctx.save_for_backward(x, saved)
-    if holder is not None:
-      holder.x, holder.saved, holder.bits = x, saved, bits
     return y
 
   @staticmethod
@@ -118,30 +114,26 @@ class _FusedBNFn(torch.autograd.Function):
     else:
       (x, saved), bits = ctx.saved_tensors, None
     dy = dy.contiguous()
-    # sum dz / sum dz * xhat already taken by the kernel that produced dy (the sole consumer's dgrad epilogue)?
-    h, part = ctx.holder, None
-    if h is not None:
-      if h.partials is not None and h.dx_ptr == dy.data_ptr():
-        part = h.partials
-      h.partials = h.x = h.saved = h.bits = None
+    if ctx.pending is not None:
+      ctx.pending.x = ctx.pending.saved = None
     if ctx.apply_holder is not None:
       # reductions + finalize only; the apply pass runs on the dY load of the conv that produced x, which receives dy itself
       coef = ops.bn_bwd_reduce(x, dy, bn.gamma.data, saved, True, bits, bn.gamma.grad, bn.beta.grad)
       ctx.apply_holder.fill(dy, x, bits, saved, coef)
       ctx.addend_holder.fill(dy, bits)
-      return dy, dy, None, None, None, None, None, None, None
+      return dy, dy, None, None, None, None, None, None
     if ctx.addend_holder is not None:
       # the residual's consumer (the block's first conv, pruning_layers._MaskedConvForkFn) masks on the fly: its gradient is
       # dy where the ReLU was on, so dy itself travels with the ReLU bits and the masked copy is never written
       dx, _ = ops.bn_bwd(x, None, dy, bn.gamma.data, saved, ctx.relu, bn.gamma.grad, bn.beta.grad, want_dres=False,
-                         relu_bits=bits, partials=part)
+                         relu_bits=bits)
       ctx.addend_holder.fill(dy, bits)
-      return dx, dy, None, None, None, None, None, None, None
+      return dx, dy, None, None, None, None, None, None
     dx, dres = ops.bn_bwd(x, None, dy, bn.gamma.data, saved, ctx.relu,
                           bn.gamma.grad, bn.beta.grad,
                           want_dres=ctx.has_res and ctx.needs_input_grad[1],
-                          relu_bits=bits, partials=part)
-    return dx, dres, None, None, None, None, None, None, None
+                          relu_bits=bits)
+    return dx, dres, None, None, None, None, None, None
 
 
 class _BnAddBnFn(torch.autograd.Function):
@@ -221,14 +213,13 @@ class BatchNorm:
       partials = getattr(x, 'bn_partials', None)   # left by the producing conv's epilogue
       if not x.requires_grad:
         x = x.detach().requires_grad_(True)
-      holder = _BnBwdHolder(relu)
       defer = bool(_BN_ON_LOAD and consumer is not None and relu and residual is None and consumer.takes_bn_input(x))
+      pending = _BnPending() if defer else None
       apply_holder = getattr(x, 'bn_apply', None)   # left by the producing conv: its backward can take this one's apply pass
       addend_holder = getattr(residual, 'masked_addend', None)   # left by the fork that made the residual
-      y = _FusedBNFn.apply(x, residual, self, relu, partials, holder, addend_holder, defer, apply_holder)
-      y.bn_ctx = holder                            # a masked conv that is this tensor's only consumer picks it up
+      y = _FusedBNFn.apply(x, residual, self, relu, partials, pending, addend_holder, apply_holder)
       if defer:
-        y.bn_pending = holder
+        y.bn_pending = pending
       return y
     y = F.batch_norm(nchw_view(x), self.moving_mean, self.moving_variance,
                      bias_tensor(self.gamma), bias_tensor(self.beta),
@@ -277,8 +268,8 @@ class _DropoutFn(torch.autograd.Function):
 def dropout(x, rate, seed0, state, is_training=True):
   """tf.keras.layers.Dropout(rate) (resnet_model.py:224-231) with the keep mask of tf.random.stateless_uniform(seed=[seed0,
   state.step]) >= rate.  Returns ``x`` itself where it does nothing (not training, or rate 0).  The output is a fresh tensor
-  that carries none of a batch norm's hand-over attributes (bn_ctx / bn_pending / bn_partials / bn_apply): the conv behind it
-  finds no batch-norm source and the batch norm in front takes its own backward reductions."""
+  that carries none of a batch norm's hand-over attributes (bn_pending / bn_partials / bn_apply): the conv behind it
+  finds nothing a batch norm left for it."""
   if not is_training or rate == 0:
     return x
   if not 0.0 < rate < 1.0:

@@ -85,7 +85,7 @@ class WideResNet:
       net = b['conv1'](net, bn_stats=True)          # its output goes straight into bn_b: statistics from the conv epilogue
       net = b['bn_b'](net, is_training, relu=True)
       if drop:
-        net = gnn.dropout(net, self.droprate, self._dropout_seed0[i], self.dropout_state)   # (a fresh tensor: no bn_ctx for conv2)
+        net = gnn.dropout(net, self.droprate, self._dropout_seed0[i], self.dropout_state)   # (a fresh tensor: no hand-over attributes for conv2)
       net = b['conv2'](net)
       net = net + skip
     net = self.final_bn(net, is_training, relu=True)

@@ -168,11 +168,11 @@ def test_autograd_node_saves_only_the_bits():
   n, rate, seed0 = 4 * 8 * 8 * 16, 0.3, 12345
   x_cpu = _values('bf16', 0)[:n].reshape(4, 8, 8, 16)
   x = x_cpu.to(DEV).requires_grad_(True)
-  x.bn_ctx = x.bn_partials = x.bn_apply = x.bn_pending = object()     # what a batch norm / conv leaves on its output
+  x.bn_partials = x.bn_apply = x.bn_pending = object()     # what a batch norm / conv leaves on its output
   state = gnn.DropoutState(DEV)
   state.step.fill_(2)
   y = gnn.dropout(x, rate, seed0, state)
-  for attr in ('bn_ctx', 'bn_partials', 'bn_apply', 'bn_pending'):
+  for attr in ('bn_partials', 'bn_apply', 'bn_pending'):
     assert not hasattr(y, attr)
   saved = y.grad_fn.saved_tensors
   assert len(saved) == 1 and saved[0].dtype == torch.uint8 and saved[0].numel() == n // 8

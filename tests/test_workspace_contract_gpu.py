@@ -162,37 +162,6 @@ def test_bn_fwd_from_producer_partials(parts):
   assert _both_poisons(name, body, requests=False) == []
 
 
-def _bwd_partials(x, dy, on, saved, parts):
-  """[parts, 2, C]: sum dz and sum dz * xhat over ``parts`` equal row sets, in float64, stored as fp32 -- what a dgrad
-  epilogue leaves (rigl_masked_conv2d_bwd_bn)."""
-  m, c = x.shape
-  dz = dy.double() if on is None else torch.where(on, dy.double(), torch.zeros((), dtype=torch.float64, device=dy.device))
-  xhat = (x.double() - saved[0].double()) * saved[1].double()
-  return torch.stack([dz.reshape(parts, -1, c).sum(1), (dz * xhat).reshape(parts, -1, c).sum(1)], dim=1).float().contiguous()
-
-
-@pytest.mark.parametrize('parts', [512, 513])
-def test_bn_bwd_from_producer_partials(parts):
-  """bn_bwd_stats on both sides of MAX_PARTS = 512 (bn.hip:849: k_bwd_finalize<16> up to it, <4> above); the workspace
-  then only carries the coefficients, behind a partial region that stays unused."""
-  from rigl_amd import ops
-  c, rows = 64, 4
-  m = parts * rows
-  x, dy, res, gamma, beta = TB._inputs((1, 1, m, c))
-  st = R.stats_ref(x, 1e-5)
-  y, saved, bits = ops.bn_fwd(x, gamma, beta, None, None, 0.1, 1e-5, True, res, want_relu_bits=True)
-  on = R.unpack_bits(bits, x.shape)
-  partials = _bwd_partials(x, dy, on, saved, parts)
-  name = 'bn_bwd from %d partials' % parts
-
-  def body():
-    dg, db = torch.empty(c, device=DEV), torch.empty(c, device=DEV)
-    dx, dres = ops.bn_bwd(x, None, dy, gamma, saved, True, dg, db, want_dres=True, relu_bits=bits, partials=partials)
-    R.check_backward(name, x, dy, on, gamma, st, dx, dg, db, dres)
-    return dx, dres, dg, db
-  _both_poisons(name, body, want_bytes=_bn_bytes(m, c))
-
-
 @pytest.mark.parametrize('m,c', [(1000, 64), (512 * 9 - 1, 2048)], ids=['1000x64', '4607x2048'])
 def test_bn_bwd_reduce_and_statistics(m, c):
   """bn_bwd_reduce (reduce + finalize, the coefficients in the caller's tensor) against bn_bwd's own bits and the float64
@@ -604,8 +573,6 @@ def _conv_call(name, case, which):
       'rigl_masked_conv2d_wgrad': lambda b, ws, n: lib.rigl_masked_conv2d_wgrad(C.byref(d), x(b), dy(b), dw(b), ws, n, st),
       'rigl_masked_conv2d_bwd': lambda b, ws, n: lib.rigl_masked_conv2d_bwd(
           C.byref(d), x(b), dy(b), w(b), b.inp(nx * 2), dw(b), dx(b), ws, n, st),
-      'rigl_masked_conv2d_bwd_bn': lambda b, ws, n: lib.rigl_masked_conv2d_bwd_bn(
-          C.byref(d), x(b), dy(b), w(b), None, dw(b), dx(b), ws, n, None, st),
       'rigl_masked_conv2d_bwd_sub': lambda b, ws, n: lib.rigl_masked_conv2d_bwd_sub(
           C.byref(d), x(b), dy(b), w(b), b.inp(nx * 2), 2, 2, dw(b), dx(b), ws, n, st),
       'rigl_masked_conv2d_bwd_relu': lambda b, ws, n: lib.rigl_masked_conv2d_bwd_relu(
@@ -651,8 +618,6 @@ def _bn_call(name):
       # bn.hip bn_bwd_impl: the check follows the argument checks and precedes make_geom and every launch
       'rigl_bn_bwd': lambda b, ws, n: lib.rigl_bn_bwd(m, c, t(b), None, b.inp(m * c // 8), t(b), v(b), v(b), v(b), v(b), v(b), 1, o(b),
                                                       o(b), r(b), r(b), ws, n, st),
-      'rigl_bn_bwd_stats': lambda b, ws, n: lib.rigl_bn_bwd_stats(m, c, t(b), None, b.inp(m * c // 8), t(b), v(b), v(b), v(b), v(b),
-                                                                  v(b), 1, o(b), o(b), r(b), r(b), b.inp(8 * 2 * c * 4), 8, ws, n, st),
       'rigl_bn_bwd_reduce': lambda b, ws, n: lib.rigl_bn_bwd_reduce(m, c, t(b), b.inp(m * c // 8), t(b), v(b), v(b), v(b), 1, r(b), r(b),
                                                                     b.out(3 * c * 4), ws, n, st),
   }
@@ -724,7 +689,6 @@ REFUSALS = [
     ('rigl_masked_conv2d_fwd_relu', lambda n: _conv_call(n, SMALL_CIN, 0)),
     ('rigl_masked_conv2d_wgrad', lambda n: _conv_call(n, ORDINARY, 2)),
     ('rigl_masked_conv2d_bwd', lambda n: _conv_call(n, ORDINARY, 2)),
-    ('rigl_masked_conv2d_bwd_bn', lambda n: _conv_call(n, ORDINARY, 2)),
     ('rigl_masked_conv2d_bwd_sub', lambda n: _conv_call(n, ORDINARY, 2)),
     ('rigl_masked_conv2d_bwd_relu', lambda n: _conv_call(n, ORDINARY, 2)),
     ('rigl_masked_conv2d_bwd_grid', lambda n: _conv_call(n, GRID, 2)),
@@ -733,7 +697,7 @@ REFUSALS = [
     ('rigl_masked_conv2d_wgrad_f32', lambda n: _conv_call(n, F32, 2)),
     ('rigl_depthwise_conv2d_wgrad', lambda n: _conv_call(n, DEPTHWISE, 2)),
     ('rigl_bn_fwd', _bn_call), ('rigl_bn_fwd_stats', _bn_call), ('rigl_bn_fwd_statistics', _bn_call),
-    ('rigl_bn_add_bn_fwd', _bn_call), ('rigl_bn_bwd', _bn_call), ('rigl_bn_bwd_stats', _bn_call), ('rigl_bn_bwd_reduce', _bn_call),
+    ('rigl_bn_add_bn_fwd', _bn_call), ('rigl_bn_bwd', _bn_call), ('rigl_bn_bwd_reduce', _bn_call),
     ('rigl_bn_add_bn_bwd', _bn_call), ('rigl_bn_relu_maxpool_bwd', _bn_call),
     ('rigl_prune_regrow', _k2_call), ('rigl_prune_regrow_slots', _k2_call), ('rigl_prune_regrow_selections', _k2_call),
     ('rigl_prune_regrow_selections_slots', _k2_call), ('rigl_topk_mask', _k2_call), ('rigl_topk_mask_batched', _k2_call),
@@ -750,7 +714,7 @@ def test_the_lists_cover_every_entry_point_of_the_header_that_takes_a_workspace(
   text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
   takes = {m.group(1) for m in re.finditer(r'\bint\s+(rigl_\w+)\s*\(([^;]*?)\)\s*;', text, flags=re.S)
            if re.search(r'\bworkspace_bytes\b', m.group(2))}
-  assert len(takes) == 32
+  assert len(takes) == 30
   assert takes == {r[0] for r in REFUSALS} | set(IGNORED)
 
 
