@@ -519,6 +519,43 @@ int rigl_grad_accumulate(int64_t n, float* acc, float* grad, int32_t mode,
                          float* loss_mean /* device [1], written in LAST only */,
                          float inv_k, int32_t max_blocks, rigl_stream_t stream);
 
+/* The same pass over up to RIGL_ACC_MAX_RANGES ranges of the two arenas, in
+ * ONE launch: element i of every range [offset, offset + length) takes the
+ * arithmetic of rigl_grad_accumulate (one IEEE fp32 addition, FIRST a bit
+ * copy); nothing outside the ranges is read or written, in either arena.
+ *   Replaces: the same cross-replica sum, where micro-batch accumulation
+ *   meets the data-parallel exchange: the LAST pass of one exchange bucket
+ *   right before its all-reduce, and the head of the kernel segment plus the
+ *   BN / bias segment behind the last backward node (rigl_amd/dist.py).
+ * `ranges` is a HOST array, consumed before the call returns and passed to
+ * the kernel by value (capture-safe).  Offsets and lengths are in elements of
+ * the arenas of n fp32; an offset is a multiple of 4 (so that every range
+ * starts 16-byte aligned), a length is arbitrary (its % 4 tail is handled)
+ * and may be 0; ranges ascend and do not overlap (they may touch).  Tiles are
+ * cut over the concatenation of the ranges -- every range rounded up to whole
+ * 16-byte quads -- so a short range behind a long one costs neither a second
+ * launch nor a tail of idle workgroups.  The result bits depend on the
+ * operands alone: not on the grid, on max_blocks or on how the same elements
+ * are cut into ranges.  The loss scalar is handled ONCE per launch by one
+ * lane, whatever n_ranges is; n_ranges == 0 with a loss still does the loss
+ * arithmetic (and without one launches nothing).
+ * RIGL_EINVAL, with nothing launched or written: everything
+ * rigl_grad_accumulate refuses, n_ranges < 0 or > RIGL_ACC_MAX_RANGES, a NULL
+ * table with n_ranges > 0, a negative offset or length, an offset that is not
+ * a multiple of 4, a range that ends beyond n, ranges that overlap or do not
+ * ascend. */
+#define RIGL_ACC_MAX_RANGES 8
+typedef struct RiglAccRange {
+  int64_t offset;  /* first element, a multiple of 4 */
+  int64_t length;  /* elements, >= 0 */
+} RiglAccRange;
+int rigl_grad_accumulate_ranges(int64_t n, float* acc, float* grad,
+                                const RiglAccRange* ranges /* host */, int32_t n_ranges,
+                                int32_t mode, const float* loss /* device [1], nullable */,
+                                float* loss_acc /* device [1] */,
+                                float* loss_mean /* device [1], written in LAST only */,
+                                float inv_k, int32_t max_blocks, rigl_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Training-state snapshots: a table of device regions <-> ONE packed device
  * image, at copy rate, with a digest per region.

@@ -105,6 +105,12 @@ SUMMARY_GROUP_BYTES = 48      # 3 fp64 (sumsq_g, sumsq_w, l1_w), 3 int64 (nz_w, 
 
 ACC_FIRST, ACC_ADD, ACC_LAST = 0, 1, 2   # RIGL_ACC_*: the modes of rigl_grad_accumulate
 ACC_TILE = 4096               # elements per block and iteration of rigl_grad_accumulate (256 lanes x 4 float4)
+ACC_MAX_RANGES = 8            # RIGL_ACC_MAX_RANGES: ranges per rigl_grad_accumulate_ranges launch
+
+
+class AccRange(C.Structure):
+  """RiglAccRange: one range of rigl_grad_accumulate_ranges, in elements."""
+  _fields_ = [('offset', C.c_int64), ('length', C.c_int64)]
 
 
 class SummaryEntry(C.Structure):
@@ -161,6 +167,7 @@ SIGNATURES = {
     'rigl_summary_workspace_bytes': (_SZ, [C.POINTER(SummaryEntry), _I32]),
     'rigl_summary_step': (C.c_int, [C.POINTER(SummaryEntry), _I32, _F, _P, _P, _F, _P, _P, _I32, _P, _SZ, _I32, _P]),
     'rigl_grad_accumulate': (C.c_int, [_I64, _P, _P, _I32, _P, _P, _P, _F, _I32, _P]),
+    'rigl_grad_accumulate_ranges': (C.c_int, [_I64, _P, _P, C.POINTER(AccRange), _I32, _I32, _P, _P, _P, _F, _I32, _P]),
     'rigl_state_packed_bytes': (_SZ, [C.POINTER(StateRegion), _I32]),
     'rigl_state_workspace_bytes': (_SZ, [C.POINTER(StateRegion), _I32]),
     'rigl_state_gather': (C.c_int, [C.POINTER(StateRegion), _I32, _P, _P, _P, _SZ, _I32, _P]),

@@ -359,8 +359,11 @@ class TrainingState:
   def _check_quiet(self, what):
     if self._on_gpu and torch.cuda.is_current_stream_capturing():
       raise RuntimeError('TrainingState.%s during graph capture: a captured copy would replay a frozen image' % what)
+    # a MicroBatches sum is pending: between its call and the LAST pass, or, under data parallelism, while its exchange is held
+    # (passes 1..k-1) or handed the LAST pass (the k-th backward)
     acc = getattr(self._inner, 'accumulation', None)
-    if acc is not None and getattr(acc, '_pending', None) is not None:
+    sync = getattr(self._inner, '_grad_sync', None)
+    if (acc is not None and getattr(acc, '_pending', None) is not None) or getattr(sync, 'exchange_pending', False):
       raise RuntimeError('TrainingState.%s while the sum of a MicroBatches call is pending: finish the step first' % what)
 
   def _scalars(self):

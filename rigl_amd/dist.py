@@ -16,6 +16,12 @@ layers of a bucket have produced their gradients (backward walks the arena
 from its end to its start), so communication overlaps the remaining backward
 kernels.  The mean (1/world) is folded into the update kernel's ``grad_scale``;
 the mask update consumes the raw sum, like the reference.
+
+With ``train.MicroBatches`` (k micro-batches per step: the reference's 8 replicas x 4 per-core batches) there is still ONE
+exchange per optimizer step.  Passes 1..k-1 hold it (``held``); in the k-th pass a bucket that becomes ready first gets the
+accumulated sum over exactly its range (``before_exchange``: one ``ops.grad_accumulate_ranges`` LAST launch on the compute
+stream) and then its all-reduce, so the exchange overlaps the k-th backward as it overlaps a plain step's; the final flush is
+one LAST launch over both of its ranges, which also carries the step's loss arithmetic.
 """
 import os
 import time
@@ -51,7 +57,19 @@ class GradSync:
     self._t_first = None
     self._timeline_events = False
     self._wait_events = None
+    # micro-batch accumulation (train.MicroBatches): while ``held`` a backward pass exchanges nothing -- passes 1..k-1 of a
+    # step, whose gradients are partial sums -- and ``before_exchange(ranges, final)``, when set, is called on the compute
+    # stream in front of every collective of the k-th pass with the arena ranges [(lo, hi)] it is about to send, so that a
+    # range gets the accumulated sum right before it leaves.  ``final``: the flush behind backward (it is called there with
+    # an empty list too).
+    self.held = False
+    self.before_exchange = None
     graph.grad_sync = self
+
+  @property
+  def exchange_pending(self):
+    """True inside an accumulated step: the exchange is held (passes 1..k-1) or handed the LAST pass (the k-th backward)."""
+    return self.held or self.before_exchange is not None
 
   # ---- instrumentation ---------------------------------------------------------
   def reset_timeline(self, device_events=True):
@@ -137,7 +155,7 @@ class GradSync:
     """Backward produces kernel gradients from the end of the arena towards
     its start; a bucket is sent as soon as a contiguous tail of at least
     ``bucket_elems`` has been produced (out-of-order arrivals just wait)."""
-    if not self.enabled:
+    if not self.enabled or self.held:
       return
     if self._hi is None:
       self._begin_step()
@@ -147,6 +165,8 @@ class GradSync:
       lo = self._vars[self._ptr].offset
       self._ptr -= 1
     if lo is not None and self._hi - lo >= self.bucket_elems:
+      if self.before_exchange is not None and self._hi > lo:
+        self.before_exchange([(lo, self._hi)], False)
       self._launch(lo, self._hi)
       self._hi = lo
 
@@ -173,6 +193,8 @@ class GradSync:
     g = self.graph
     end = g.G.numel()
     parts = [(lo, h) for lo, h in ((0, hi), (kend, end)) if h > lo]
+    if self.before_exchange is not None:
+      self.before_exchange(parts, True)        # both ranges in one launch, with the step's loss arithmetic
     if not parts:
       return
     if len(parts) == 2 and g.G.is_cuda and dist.get_backend(self.group) == 'nccl':
@@ -192,7 +214,7 @@ class GradSync:
     """Called once after backward: flushes what is left (the head of the kernel
     segment, the BN/bias segment) and makes the compute stream wait."""
     del graph
-    if not self.enabled:
+    if not self.enabled or self.held:
       self._reset()
       return
     g = self.graph

@@ -423,6 +423,29 @@ def grad_accumulate(acc, grad, mode, loss=None, loss_acc=None, loss_mean=None, i
                                          _ptr(loss_mean), float(inv_k), int(max_blocks), _stream()))
 
 
+def grad_accumulate_ranges(acc, grad, ranges, mode, loss=None, loss_acc=None, loss_mean=None, inv_k=1.0, max_blocks=0):
+  """grad_accumulate over ``ranges`` of the two arenas only, in one launch (rigl_grad_accumulate_ranges): a sequence of up to
+  _lib.ACC_MAX_RANGES ``(offset, length)`` pairs in elements, ascending and not overlapping, every offset a multiple of 4, a
+  length arbitrary (0 is legal).  Nothing outside the ranges is read or written.  The loss arithmetic of ``mode`` is done once
+  per launch, with an empty ``ranges`` too.  One launch, capture-safe."""
+  _req(acc, torch.float32, 'acc')
+  _req(grad, torch.float32, 'grad')
+  _req(loss, torch.float32, 'loss', allow_none=True)
+  _req(loss_acc, torch.float32, 'loss_acc', allow_none=True)
+  _req(loss_mean, torch.float32, 'loss_mean', allow_none=True)
+  if acc.numel() != grad.numel():
+    raise ValueError('size mismatch: acc has %d elements, grad %d' % (acc.numel(), grad.numel()))
+  for t, name in ((loss, 'loss'), (loss_acc, 'loss_acc'), (loss_mean, 'loss_mean')):
+    if t is not None and t.numel() != 1:
+      raise ValueError('%s must hold 1 float' % name)
+  ranges = list(ranges)
+  arr = (_lib.AccRange * max(len(ranges), 1))()
+  for i, (off, length) in enumerate(ranges):
+    arr[i].offset, arr[i].length = int(off), int(length)
+  check(_lib.load().rigl_grad_accumulate_ranges(acc.numel(), _ptr(acc), _ptr(grad), arr, len(ranges), int(mode), _ptr(loss),
+                                                _ptr(loss_acc), _ptr(loss_mean), float(inv_k), int(max_blocks), _stream()))
+
+
 def state_table(tensors):
   """The host table of rigl_state_gather / rigl_state_scatter: one region per tensor (contiguous, on one GPU, a whole number
   of 4-byte words).  The table holds raw pointers: the caller keeps the tensors alive."""

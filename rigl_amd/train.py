@@ -122,12 +122,18 @@ class GradientDescentOptimizer(Optimizer):
       acc.check_pending(loss)      # a sum pending for another loss: refused, never guessed
     if loss is not None and self._backward_done_for is not loss:
       g.zero_other_grads()
-      loss.backward()
-      self._backward_done_for = loss
-      if acc is not None:
-        acc.finish(loss)           # the LAST pass of a pending sum: the arena holds the raw sum before anything reads it
-      if self._grad_sync is not None:
-        self._grad_sync.all_reduce(g)
+      # a sum pending for this loss under a gradient exchange: the LAST pass runs range by range in front of each collective
+      exchanged = acc is not None and acc.arm_exchange(loss)
+      try:
+        loss.backward()
+        self._backward_done_for = loss
+        if acc is not None and not exchanged:
+          acc.finish(loss)         # the LAST pass of a pending sum: the arena holds the raw sum before anything reads it
+        if self._grad_sync is not None:
+          self._grad_sync.all_reduce(g)
+      finally:
+        if exchanged:
+          acc.disarm_exchange()
     if var_list is not None:
       return [(v.grad, v) for v in var_list]
     # (the list handed out is remembered: getting it back untouched needs no per-variable check in apply_gradients)
@@ -379,8 +385,20 @@ class MicroBatches:
   into whatever is being captured and every buffer (the second arena, the loss accumulator and mean) is allocated here, so
   GraphedStep(mb, ...) captures and replays the k passes and the update as one graph.
 
-  Not combined with data parallelism yet: an enabled GradSync (world > 1) raises NotImplementedError -- its bucket exchange
-  starts inside every backward pass and would have to be held back to the last micro-batch; that is a follow-up."""
+  With data parallelism (the inner optimizer's ``grad_sync`` is an enabled dist.GradSync -- world > 1, or forced on with one rank)
+  this is the reference's headline configuration, replicas x per-core batches (8 x 4 x 128 = 4096), with ONE gradient exchange
+  per optimizer step.  Passes 1..k-1 hold the exchange: no collective is enqueued, each is followed by the whole-arena FIRST /
+  ADD pass as above.  In the k-th backward pass every exchange bucket [lo, hi) that becomes ready first gets a LAST pass over
+  exactly that range (ops.grad_accumulate_ranges, on the compute stream) and then its asynchronous all-reduce, so the exchange
+  overlaps the k-th backward bucket by bucket like a plain data-parallel step's; the final flush behind backward is one LAST
+  launch over the head of the kernel segment and the BN / bias segment, which carries the loss arithmetic, followed by the
+  coalesced collective.  Every element of the arena gets LAST exactly once and the whole-arena LAST is not run.  The arena then
+  holds the raw sum over ranks AND micro-batches -- fl(S_0 + S_1 + ...) of the ranks' sequential micro-batch sums S_r -- which
+  the mask update, DNW, pruning and the summaries read; update_scale() is 1 / world x 1 / k, the one place either factor lives.
+  ``mb.loss`` stays the RANK-LOCAL mean of this rank's k micro-batch losses (the reference logs the per-core loss, too); reduce
+  it over ranks yourself where a global figure is wanted.  k == 1 with a GradSync enqueues exactly what a plain data-parallel
+  step enqueues.  GraphedStep runs data-parallel steps eagerly, accumulated or not.  A GradSync that exchanges another graph's
+  arena than the optimizer's is refused (NotImplementedError): its buckets would not be ranges of the arena summed here."""
 
   def __init__(self, loss_fn, optimizer, micro_batches):
     k = int(micro_batches)
@@ -390,9 +408,12 @@ class MicroBatches:
     if not hasattr(inner, 'accumulation'):
       raise TypeError('%s cannot accumulate (expected a rigl_amd.train optimizer or a wrapper around one)' % type(inner).__name__)
     sync = getattr(inner, '_grad_sync', None)
-    if sync is not None and getattr(sync, 'enabled', False):
-      raise NotImplementedError('MicroBatches with an enabled GradSync (world > 1): accumulation is not combined with the '
-                                'in-backward bucket exchange yet')
+    if sync is None or not getattr(sync, 'enabled', False):
+      sync = None
+    elif getattr(sync, 'graph', None) is not inner.graph:
+      raise NotImplementedError('MicroBatches: the GradSync does not exchange the gradient arena of the optimizer\'s graph; '
+                                'holding and finishing the exchange of another arena is not supported')
+    self._sync = sync              # the enabled GradSync whose exchange is held back to the k-th pass, or None
     self._loss_fn = loss_fn
     self._inner = inner
     self.micro_batches = k
@@ -444,14 +465,21 @@ class MicroBatches:
     # that stream into its capture.  So the references taken here live from this call to the apply (or the next call).
     self._pending = self._done_for = None
     inner.forget_backward()
-    for i in range(self.micro_batches - 1):
-      loss = self._loss_fn(*args, **kwargs)
-      scalar = self._check_loss(loss)
-      g.zero_other_grads()
-      loss.backward()
-      ops.grad_accumulate(self._arena, g.G, _lib.ACC_FIRST if i == 0 else _lib.ACC_ADD,
-                          loss=scalar, loss_acc=self._loss_acc)
-      del loss, scalar
+    sync = self._sync
+    if sync is not None:
+      sync.held = True             # these passes' gradients are partial sums: nothing is exchanged, no bucket state is kept
+    try:
+      for i in range(self.micro_batches - 1):
+        loss = self._loss_fn(*args, **kwargs)
+        scalar = self._check_loss(loss)
+        g.zero_other_grads()
+        loss.backward()
+        ops.grad_accumulate(self._arena, g.G, _lib.ACC_FIRST if i == 0 else _lib.ACC_ADD,
+                            loss=scalar, loss_acc=self._loss_acc)
+        del loss, scalar
+    finally:
+      if sync is not None:
+        sync.held = False
     loss = self._loss_fn(*args, **kwargs)
     self._check_loss(loss)
     self._pending = loss
@@ -470,6 +498,30 @@ class MicroBatches:
       return
     ops.grad_accumulate(self._arena, self._inner.graph.G, _lib.ACC_LAST, loss=loss.detach(),
                         loss_acc=self._loss_acc, loss_mean=self._loss_mean, inv_k=self.inv_k)
+    self._pending, self._done_for = None, loss
+
+  def arm_exchange(self, loss):
+    """In front of the backward pass of ``loss``: with a gradient exchange and the sum pending for exactly this tensor, the
+    LAST pass is handed to the exchange (True) -- range by range in front of each collective -- and finish() is not to run."""
+    if self._sync is None or self._pending is None or self._pending is not loss:
+      return False
+    self._sync.before_exchange = self._last_ranges
+    return True
+
+  def disarm_exchange(self):
+    self._sync.before_exchange = None
+
+  def _last_ranges(self, ranges, final):
+    """GradSync.before_exchange: the LAST pass over the arena ranges [(lo, hi)] about to be sent; the flush behind backward
+    (``final``) carries the loss arithmetic and ends the pending sum."""
+    spans = [(lo, hi - lo) for lo, hi in ranges]
+    G = self._inner.graph.G
+    if not final:
+      ops.grad_accumulate_ranges(self._arena, G, spans, _lib.ACC_LAST)
+      return
+    loss = self._pending
+    ops.grad_accumulate_ranges(self._arena, G, spans, _lib.ACC_LAST, loss=loss.detach(), loss_acc=self._loss_acc,
+                               loss_mean=self._loss_mean, inv_k=self.inv_k)
     self._pending, self._done_for = None, loss
 
   def finished_for(self, loss):
