@@ -6,6 +6,15 @@ captured graph that holds ``next_batch()`` replays fresh batches across epoch bo
   DeviceCifar(images_u8, labels, batch, ...)   the loader; call ``next_batch()`` at the top of a GraphedStep's loss_fn
   load_cifar10_python(dir, split)              the standard cifar-10-batches-py pickles -> the two arrays DeviceCifar takes
   pad_input / preprocess_train                 host restatements on arrays, for parity reading (never on the training path)
+
+The ImageNet image store (host side only; the reference constructs ``official.resnet.imagenet_input.ImageNetInput``, which it
+does not vendor): DECODED uint8 RGB images of any size packed into one flat array with offsets / dims / labels tables -- the
+format a device loader reads.  The device pipeline over it (crop, bicubic resize, flip, normalise) is specified bit for bit in
+tests/imagenet_input_ref.py and not built yet; JPEG decoding happens once, on the host.
+
+  pack_image_store / save_image_store / load_image_store   the store: flat uint8 + offsets / dims / labels tables
+  image_store_from_folder(root, short_side)                decode (PIL) and short-side-resize a class/xxx.JPEG tree
+  check_image_table(store_bytes, offsets, dims)            refuses a table row that does not lie inside the store
 """
 import os
 import pickle
@@ -133,3 +142,93 @@ def input_fn(params, **kw):
   split = params['data_split']
   images, labels = load_cifar10_python(params['data_directory'], split)
   return DeviceCifar(images, labels, params['batch_size'], train=split == 'train', **kw)
+
+
+# ---- the ImageNet image store ------------------------------------------------------------------------------------------
+MAX_IMAGE_SIDE = 4096
+STORE_FILES = ('store.u8', 'offsets.npy', 'dims.npy', 'labels.npy')
+
+
+def pack_image_store(arrays, labels):
+  """(store uint8 flat, offsets int64 [n], dims int32 [n, 2] = (h, w), labels int32 [n]) from a list of HWC uint8 RGB arrays:
+  the images tightly packed one after the other (row stride 3 w, no alignment)."""
+  arrays = [np.asarray(a) for a in arrays]
+  labels = np.asarray(labels, dtype=np.int32).reshape(-1)
+  if len(arrays) != labels.size:
+    raise ValueError('%d labels for %d images' % (labels.size, len(arrays)))
+  for j, a in enumerate(arrays):
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+      raise ValueError('image %d must be uint8 [h, w, 3] (HWC RGB), got %s %s' % (j, a.dtype, a.shape))
+  dims = np.array([a.shape[:2] for a in arrays], dtype=np.int32).reshape(-1, 2)
+  sizes = 3 * dims[:, 0].astype(np.int64) * dims[:, 1].astype(np.int64)
+  offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64) if len(arrays) else np.zeros(0, np.int64)
+  store = np.concatenate([a.reshape(-1) for a in arrays]) if len(arrays) else np.zeros(0, np.uint8)
+  return store, offsets, dims, labels
+
+
+def save_image_store(directory, store, offsets, dims, labels):
+  """Writes the four files of a store: raw ``store.u8`` and ``offsets.npy`` / ``dims.npy`` / ``labels.npy``."""
+  os.makedirs(directory, exist_ok=True)
+  np.asarray(store, dtype=np.uint8).reshape(-1).tofile(os.path.join(directory, STORE_FILES[0]))
+  np.save(os.path.join(directory, STORE_FILES[1]), np.asarray(offsets, dtype=np.int64).reshape(-1))
+  np.save(os.path.join(directory, STORE_FILES[2]), np.asarray(dims, dtype=np.int32).reshape(-1, 2))
+  np.save(os.path.join(directory, STORE_FILES[3]), np.asarray(labels, dtype=np.int32).reshape(-1))
+
+
+def load_image_store(directory, mmap=True):
+  """(store, offsets, dims, labels) as save_image_store wrote them; the store is an ``np.memmap`` (read-only) when ``mmap``."""
+  for name in STORE_FILES:
+    if not os.path.exists(os.path.join(directory, name)):
+      raise FileNotFoundError('no %s in %r: an image store holds %s (save_image_store / image_store_from_folder)' % (
+          name, directory, ', '.join(STORE_FILES)))
+  path = os.path.join(directory, STORE_FILES[0])
+  if os.path.getsize(path) == 0:
+    store = np.zeros(0, np.uint8)
+  else:
+    store = np.memmap(path, dtype=np.uint8, mode='r') if mmap else np.fromfile(path, dtype=np.uint8)
+  return (store,) + tuple(np.load(os.path.join(directory, n)) for n in STORE_FILES[1:])
+
+
+def image_store_from_folder(root, short_side=None, extensions=('.jpeg', '.jpg', '.png')):
+  """Decodes a ``root/<class>/<file>`` tree into a store (classes in sorted order are labels 0, 1, ...; files in sorted
+  order).  With ``short_side`` every image is resized (PIL, bicubic) so that its shorter side has that length; that resize is a
+  resolution trade made once on the host and not part of the pinned pipeline.  Host-only.  Returns pack_image_store's
+  tuple plus the class names."""
+  try:
+    from PIL import Image  # pylint: disable=import-outside-toplevel
+  except ImportError as e:
+    raise ImportError('image_store_from_folder decodes with PIL (pillow), which is not installed; build the store on a '
+                      'machine that has it, or pack decoded arrays with pack_image_store') from e
+  classes = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d)))
+  if not classes:
+    raise FileNotFoundError('no class folder in %r' % (root,))
+  arrays, labels = [], []
+  for label, cls in enumerate(classes):
+    for name in sorted(os.listdir(os.path.join(root, cls))):
+      if not name.lower().endswith(tuple(extensions)):
+        continue
+      with Image.open(os.path.join(root, cls, name)) as im:
+        im = im.convert('RGB')
+        if short_side is not None and min(im.size) != int(short_side):
+          k = float(short_side) / min(im.size)
+          w, h = (max(1, int(round(v * k))) for v in im.size)
+          im = im.resize((w, h), Image.BICUBIC)
+        arrays.append(np.asarray(im, dtype=np.uint8))
+      labels.append(label)
+  return pack_image_store(arrays, labels) + (classes,)
+
+
+def check_image_table(store_bytes, offsets, dims):
+  """Raises ValueError naming the first row that does not describe an image inside the store: 1 <= h, w <= 4096,
+  offset >= 0, offset + 3 h w <= store_bytes."""
+  offsets, dims = np.asarray(offsets), np.asarray(dims)
+  if offsets.ndim != 1 or dims.shape != (offsets.size, 2):
+    raise ValueError('offsets must be [n] and dims [n, 2], got %s and %s' % (offsets.shape, dims.shape))
+  off, h, w = offsets.astype(np.int64), dims[:, 0].astype(np.int64), dims[:, 1].astype(np.int64)
+  side = (h >= 1) & (h <= MAX_IMAGE_SIDE) & (w >= 1) & (w <= MAX_IMAGE_SIDE)
+  need = 3 * np.where(side, h * w, 0)
+  bad = ~(side & (off >= 0) & (need <= store_bytes) & (off <= store_bytes - need))
+  if bad.any():
+    j = int(np.argmax(bad))
+    raise ValueError('image table row %d is bad: h %d, w %d (must be 1 .. %d), offset %d, %d bytes needed of a store of %d' % (
+        j, h[j], w[j], MAX_IMAGE_SIDE, off[j], 3 * h[j] * w[j], store_bytes))
